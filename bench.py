@@ -19,6 +19,10 @@ round-2 form).  `python bench.py --gpus N` launches the N ranks itself when it w
 
 `--workload spanning` = BASELINE config[4] shape (breakend loci, 200 reads x 250 bp, mixed k): an extra measurement.
 
+A plain run does what the headline figure needs: set up, warm up, time --steps steps, print the line.  `--full` adds the parity
+checks, the roofline / algorithmic-byte figures, the extra legs and the CPU baseline.  `--dump-outputs DIR` writes what the timed
+path returned in its last step (dump_outputs below), so that two builds can be compared output for output.
+
 Prints ONE JSON line (DESIGN.md "Measurement" defines roofline / cpu_baseline).
 """
 import argparse
@@ -68,6 +72,12 @@ def parse_args():
     ap.add_argument("--mix", action="store_true",
                     help="N > 1, --queue node: every 4th rank part holds loci with 2.5x the reads (NOT the metric's configuration) -- makes the "
                          "queue's balancing visible in loci_per_rank")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: parity checks against the reference digests and the CPU restatement, "
+                         "roofline and algorithmic-byte figures, the extra legs (kernel_only, packed_input, mixed_shape, spanning, "
+                         "refiner_batch) and the CPU baseline; --no-extras / --no-cpu-baseline trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32/float64, rank 0)")
     return ap.parse_args()
 
 
@@ -153,6 +163,76 @@ def result_blob(out):
              np.frombuffer(out.aligns, dtype=np.uint8)[:n_contigs * (64 if out.kind == "smallsv" else 64)],
              out.seq[:out.used[0].value], out.bits[:out.used[1].value].view(np.uint8), out.cig[:out.used[2].value].view(np.uint8)]
     return np.concatenate(parts)
+
+
+DUMP_MAX_LOCI = 16384        # larger batches: a fixed sample (seed 0) of this many loci
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out, path):
+    """What the caller of the batch call received, written as .npy without the arena layout (offsets dropped, so two builds that lay
+    the arenas out differently still compare equal): per locus its result record; per contig, in locus order, its contig and
+    alignment records; and the arena slices each contig owns (bases, support / reject read bits, CIGAR ops) concatenated in the
+    same order.  Integers as float64 (exact), bases as float32.  The sample is cut to DUMP_MAX_BYTES at a locus boundary.  An array
+    with nothing in it is not written (pseudo contigs: none on the config-2 workload; their count per locus is in loci.npy)."""
+    res, ctg, aln = _records(out.res), _records(out.contigs), _records(out.aligns)
+    aln_cols = [col for name, col in _leaf_fields(aln) if not name.endswith("_off") and name != "reserved"]
+    n = len(res)
+    ids = np.arange(n) if n <= DUMP_MAX_LOCI else np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_LOCI, replace=False))
+    seq, bits, cig = out.seq, out.bits.view(np.uint32), out.cig
+    rows = dict(loci=[], contigs=[], contig_seq=[], contig_support=[], contig_reject=[], cigar=[], pseudo_len=[], pseudo_seq=[])
+    total = 0
+    for l in ids:
+        r = res[l]
+        part = dict(loci=[[l, r["status"], r["n_contigs"], r["n_words"], r["n_pseudo"], r["final_word_length"], r["n_iterations"],
+                           r["cyclic_iterations"]]],
+                    contigs=[], contig_seq=[], contig_support=[], contig_reject=[], cigar=[], pseudo_len=[], pseudo_seq=[])
+        if r["status"] == 0:
+            nw = int(r["n_words"])
+            for c in range(int(r["first_contig"]), int(r["first_contig"]) + int(r["n_contigs"])):
+                cc, a = ctg[c], aln[c]["align"]
+                part["contigs"].append([l, cc["seq_len"], cc["seed_read_count"], cc["conservative_begin"], cc["conservative_end"]]
+                                       + [col[c] for col in aln_cols])
+                so, sup, rej = int(cc["seq_off"]), 2 * int(cc["support_off"]), 2 * int(cc["reject_off"])
+                part["contig_seq"].append(seq[so:so + int(cc["seq_len"])])
+                part["contig_support"].append(bits[sup:sup + 2 * nw])  # (64-bit words as two 32-bit halves: exact in float64)
+                part["contig_reject"].append(bits[rej:rej + 2 * nw])
+                for i in ("1", "2"):
+                    if int(a["cigar%s_len" % i]):
+                        part["cigar"].append(cig[int(a["cigar%s_off" % i]):int(a["cigar%s_off" % i]) + int(a["cigar%s_len" % i])])
+            off = int(r["pseudo_seq_off"])
+            for p in range(int(r["n_pseudo"])):
+                ln = int(out.bits[int(r["pseudo_len_off"]) + p])
+                part["pseudo_len"].append(ln)
+                part["pseudo_seq"].append(seq[off:off + ln])
+                off += ln
+        size = 8 * (8 + len(part["contigs"]) * (5 + len(aln_cols))) + sum((4 if k.endswith("seq") else 8) * np.size(x)
+                                                                         for k in part if k not in ("loci", "contigs") for x in part[k])
+        if total + size > DUMP_MAX_BYTES:
+            break
+        total += size
+        for k, v in part.items():
+            rows[k] += v
+    os.makedirs(path, exist_ok=True)
+    widths = dict(loci=8, contigs=5 + len(aln_cols))
+    for k, v in rows.items():
+        dt = np.float32 if k.endswith("seq") else np.float64
+        if k in widths:
+            a = np.asarray(v, dtype=dt).reshape(-1, widths[k])
+        else:
+            a = np.concatenate([np.asarray(x, dtype=dt).ravel() for x in v]) if v else np.zeros(0, dt)
+        if a.size:
+            np.save(os.path.join(path, k + ".npy"), a)
+
+
+def _records(arr):
+    """a ctypes array of result structures as a numpy record array (no copy; numpy takes the layout from the ctypes type)"""
+    return np.frombuffer(arr, dtype=np.dtype(arr._type_))
+
+
+def _leaf_fields(a):
+    """(name, column) of every scalar field of a structured array, nested records flattened"""
+    return sum(([(f, a[f])] if a.dtype[f].names is None else _leaf_fields(a[f]) for f in a.dtype.names), [])
 
 
 def main():
@@ -325,7 +405,9 @@ def main():
             bj = config2_batch(n_loci, seed=12345 + 1000003 * rank + 7919 * j, n_reads=200 if (args.mix and multi and rank % 4 == 3) else 80)
             oj = BatchOutput(lib, "smallsv", n_loci, 10, 4096 * n_loci + (1 << 20), 128 * n_loci + 4096, 512 * n_loci + 4096, pinned=not args.pageable)
             stream.append((bj, bj if args.pageable else tuple(pinned_copy(lib, a) for a in bj), oj))
-    step_i = [0]
+    # phase of the rotation: the LAST timed step runs batch 0, whatever --steps / --warmup are, so that --dump-outputs writes the same
+    # batch's results for any step count
+    step_i = [(1 - args.warmup - args.steps) % len(stream)]
     ran = [False] * len(stream)  # batches of the stream that have been through the library at least once (warm-up or timed)
 
     per_dev = [0] * n_dev
@@ -395,10 +477,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    results = out.decode(n_reads)
-    taken = [l for l, r in enumerate(results) if r["status"] != -10]  # (-10: another rank took the locus' block, node queue)
-    n_contigs = sum(len(results[l]["contigs"]) for l in taken)
-    n_fail = sum(1 for l in taken if results[l]["status"] != 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)  # (the last timed step ran batch 0: see step_i)
+    status = _records(out.res)["status"]
+    taken = [int(l) for l in np.flatnonzero(status != -10)]  # (-10: another rank took the locus' block, node queue)
+    n_contigs = int(_records(out.res)["n_contigs"][status == 0].sum())
+    n_fail = int((status[taken] != 0).sum())
+    results = out.decode(n_reads) if args.full else None  # (the checks and the byte counts below read the decoded loci)
     steps = args.steps
     loci_per_rank = [len(taken)]
     node_check = None
@@ -418,7 +503,7 @@ def main():
         return bad, n
 
     if node_queue and spanning:
-        mism, checked = span_digest_mismatches(taken)
+        mism, checked = span_digest_mismatches(taken) if args.full else (0, 0)
         dev = "cuda" if backend == "nccl" else "cpu"
         t = torch.tensor([mism, checked, n_fail, len(taken)], dtype=torch.int64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
@@ -434,9 +519,9 @@ def main():
         # restatement on a sample; the verdicts are summed over the ranks
         orc_n = OracleLib()
         dig_path = os.path.join(ROOT, "tests", "golden", "config2_digests.bin")
-        raw = open(dig_path, "rb").read() if (os.path.exists(dig_path) and n_loci == 10000 and not args.mix) else b""
+        raw = open(dig_path, "rb").read() if (args.full and os.path.exists(dig_path) and n_loci == 10000 and not args.mix) else b""
         mism = checked = 0
-        rest = [l for l in taken if l >= n_loci or not raw]
+        rest = [l for l in taken if l >= n_loci or not raw] if args.full else []
         for l in taken:
             if raw and l < n_loci:
                 mism += hashlib.sha256(small_sv_text(results[l]).encode("latin-1")).digest() != raw[32 * l:32 * l + 32]
@@ -459,7 +544,7 @@ def main():
     if proc_queue and spanning:
         loci_per_rank = list(per_dev)
         if rank == 0:
-            mism, checked = span_digest_mismatches(taken)
+            mism, checked = span_digest_mismatches(taken) if args.full else (0, 0)
             node_check = [mism, checked, n_fail, len(taken)]
             if mism or n_fail or len(taken) != n_loci * n_dev or sum(per_dev) != n_loci * n_dev:
                 raise SystemExit("PARITY FAILURE (process queue, spanning): %d of %d checked loci differ, %d loci failed, %d of %d loci taken (per device: %s)"
@@ -470,12 +555,12 @@ def main():
             # one process holds every result: part 0 is the digest workload, the other parts against the CPU restatement on a sample
             orc_n = OracleLib()
             dig_path = os.path.join(ROOT, "tests", "golden", "config2_digests.bin")
-            raw = open(dig_path, "rb").read() if (os.path.exists(dig_path) and n_loci == 10000 and not args.mix) else b""
+            raw = open(dig_path, "rb").read() if (args.full and os.path.exists(dig_path) and n_loci == 10000 and not args.mix) else b""
             mism = checked = 0
             for l in range(n_loci if raw else 0):
                 mism += hashlib.sha256(small_sv_text(results[l]).encode("latin-1")).digest() != raw[32 * l:32 * l + 32]
                 checked += 1
-            rest = [l for l in taken if l >= n_loci or not raw]
+            rest = [l for l in taken if l >= n_loci or not raw] if args.full else []
             for l in rest[::max(1, len(rest) // (16 * n_dev))]:
                 reads, ref, cuts = unpack_locus(batch, l)
                 mism += small_sv_text(results[l]) != orc_n.small_sv_locus(opts, SCORES, LARGE_INDEL, reads, ref, cuts)
@@ -493,7 +578,9 @@ def main():
         dig_path = os.path.join(ROOT, "tests", "golden", "config5_digests.bin" if spanning else "config2_digests.bin")
         raw = open(dig_path, "rb").read() if os.path.exists(dig_path) else b""
         n_dig = min(len(raw) // 32, n_loci)
-        if spanning and (node_queue or proc_queue):
+        if not args.full:
+            how = "not checked in a plain run (bench.py --full checks the results against the reference digests / the CPU restatement)"
+        elif spanning and (node_queue or proc_queue):
             checked, how = node_check[1], "reference digests (tests/golden/config5_digests.bin; every part of the node batch repeats the digest loci)" + (", summed over the ranks" if node_queue else "")
         elif spanning:
             from test_digests import c5_text
@@ -517,7 +604,9 @@ def main():
                 checked += 1
             how = "oracle spot check"
         stream_res = [results]
-        if rotate and len(stream) > 1:
+        if rotate and len(stream) > 1 and not args.full:
+            n_fail += sum(int((_records(oj.res)["status"] != 0).sum()) for j, (_, _, oj) in enumerate(stream[1:], start=1) if ran[j])
+        elif rotate and len(stream) > 1:
             # the other batches of the stream: every locus must have succeeded, a sample against the CPU restatement
             extra = 0
             for j, (bj, _, oj) in enumerate(stream[1:], start=1):
@@ -539,71 +628,14 @@ def main():
         value = loci_total / elapsed
         asm_sum, align_sum = acc["assemble_ms"], acc["align_ms"]
         if spanning:
-            b_in = sum(sum(len(x) for x in loci[i][0]) + len(loci[i][1]) + len(loci[i][2]) for i in taken)
-            b_ptr = b_out = 0
-            for i in taken:
-                r = results[i]
-                b_out += len(loci[i][0]) * 8
-                for c, a in zip(r["contigs"], r["aligns"]):
-                    q = len(c["seq"])
-                    span = (len(loci[i][1]) + len(loci[i][2])) if a["is_uncut"] else (len(loci[i][1]) + len(loci[i][2]) - 400)
-                    b_ptr += (q + 1) * (span + 2)  # 1 B cells: the reference's own jump pointer matrix (GlobalJumpAligner.hpp:81-115)
-                    b_out += q + 2 * ((len(loci[i][0]) + 7) // 8) + 64
-            asm_bytes, align_bytes, align_name = sum(sum(len(x) for x in loci[i][0]) for i in taken) + b_out, b_ptr, "align_kernel<JUMP>"
+            align_name = "align_kernel<JUMP>"
             workload = ("BASELINE config[4] shape (NOT the metric's configuration): breakend loci, 200 reads x 250 bp, 1 % N, 10 % "
                         "tandem-repeat loci, minWordLength per locus from {25..75} in ONE launch, assemble + "
                         "GlobalJumpAligner(2,-8,-12,-1,-1;-100) on 700+700 bp windows + re-align rule")
         else:
-            # (the stream's batches weighted by the timed steps each of them ran)
-            tot_w = max(1, sum(used)) if rotate else 1
-            b_in = b_ptr = b_out = asm_bytes = align_bytes = 0.0
-            for j, rj in enumerate(stream_res):
-                w = (used[j] / tot_w) if rotate else (1.0 if j == 0 else 0.0)
-                if w == 0.0 or rj is None:
-                    continue
-                bj = stream[j][0]
-                tk = taken if j == 0 else list(range(n_loci))
-                bi, bp, bo, qb, wb = algorithmic_bytes_smallsv(bj, rj, tk)
-                rin = sum(int(bj[1][bj[2][l + 1]] - bj[1][bj[2][l]]) for l in tk)
-                b_in, b_ptr, b_out = b_in + w * bi, b_ptr + w * bp, b_out + w * bo
-                asm_bytes, align_bytes = asm_bytes + w * (rin + bo), align_bytes + w * (qb + wb + bp)
             align_name = "align_kernel<LARGE_INDEL>"
             workload = ("BASELINE config[1]: synthetic small-indel loci, 80 reads/locus x150bp, k=31..76 step 5, "
                         "assemble + 10-mer trim + GlobalLargeIndelAligner(2,-8,-24,-1,-1;-100) on 1800 bp windows")
-        # dominant kernel by HIP-event time summed over the timed region.  A launch = one block's kernel; the events of
-        # different blocks overlap on the device (that is the point of the block queue), each is timed on its own stream.
-        n_blocks = max(1, acc["n_blocks"])
-        if align_sum >= asm_sum:
-            dom, dom_bytes, dom_ms, dom_launches = align_name, align_bytes * steps, align_sum, n_blocks
-            dom_note = "per block: all E-bucket launches of the block (they run concurrently on side streams)"
-        else:
-            # the assembler stage of a block: graph_kernel -> contig_kernel (asm_lds.hpp; the general assemble_kernel for what they
-            # punt and under MANTA_AMD_ASM_PATH=general), timed by the library as ONE span of HIP events on the block's stream
-            dom = "assemble_kernel" if os.environ.get("MANTA_AMD_ASM_PATH") == "general" else "assembler_stage"
-            dom_bytes, dom_ms, dom_launches = asm_bytes * steps, asm_sum, n_blocks
-            dom_note = ("one launch per block" if dom == "assemble_kernel" else
-                        "per block: graph_kernel + contig_kernel (big piles: graph_big_kernel + repeat_big_kernel + contig_big_kernel, one round per word length) + assemble_kernel on what they hand back; one HIP-event "
-                        "span, rocprofv3 lists the kernels separately: their averages add up to avg_launch_ms")
-        avg_launch_ms = dom_ms / dom_launches
-        achieved = (dom_bytes / dom_launches) / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms > 0 else 0.0
-        # roofline.traffic is NOT measured in this run: it is the HBM-side byte count of the builder's own rocprofv3 --pmc passes
-        # (tools/profile_round.sh -> profiles/traffic*.json), quoted with its source and date
-        traffic, traffic_source = None, None
-        tpath = os.path.join(ROOT, "profiles", "traffic_spanning.json" if spanning else "traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                if tj.get("loci") == n_loci and tj.get("workload", "smallsv") == args.workload:
-                    traffic = tj.get(dom)
-                    traffic_source = "%s: %s, %s" % (os.path.relpath(tpath, ROOT), tj.get("source", "builder-run rocprofv3 --pmc passes"), tj.get("date", "round 2"))
-                elif spanning and tj.get("workload") == "spanning" and tj.get("loci") and n_loci % tj["loci"] == 0 and tj.get(dom) is not None:
-                    # the spanning block TILES the distinct loci the counter passes ran on (2 048: the digest set; under the profiler larger
-                    # blocks run into the passes' time limit), so a launch's traffic is the counted bytes x the number of copies
-                    traffic = int(tj[dom] * (n_loci // tj["loci"]))
-                    traffic_source = ("%s: %s, %s; counted on %d loci, x %d: the block repeats those loci" %
-                                      (os.path.relpath(tpath, ROOT), tj.get("source", "builder-run rocprofv3 --pmc passes"), tj.get("date", ""), tj["loci"], n_loci // tj["loci"]))
-            except Exception:
-                traffic = None
         o = {
             "metric": METRIC, "value": round(value, 1), "unit": "loci/s", "n_gpus": n_dev, "steps": steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -622,17 +654,7 @@ def main():
                        "queue": "process" if proc_queue else ("node" if node_queue else "rank"), "backend": backend if multi else None,
                        "dist_world": dist.get_world_size() if multi else 1, "loci_per_rank": loci_per_rank,
                        "mix": bool(args.mix and node_queue),
-                       "parity": "%d loci vs %s: 0 mismatches" % (checked, how)},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_launch": int(dom_bytes / dom_launches), "avg_launch_ms": round(avg_launch_ms, 3),
-                         "launches": dom_launches, "note": dom_note,
-                         # extra (not the contract's fraction): the counter traffic against what this chip delivers to 64-byte
-                         # random accesses (tools/microbench/gather_ceiling.hip, DESIGN.md 5.1: 3.36 TB/s) -- the bound the kernel sits on
-                         "sector_traffic": None if not traffic or avg_launch_ms <= 0 else
-                                           {"achieved_GBps": round(traffic / (avg_launch_ms * 1e-3) / 1e9, 1), "random_access_ceiling_GBps": 3360.0,
-                                            "frac": round(traffic / (avg_launch_ms * 1e-3) / 1e9 / 3360.0, 3),
-                                            "traffic_over_algorithmic": round(traffic / max(1.0, dom_bytes / dom_launches), 1)}},
+                       "parity": ("%d loci vs %s: 0 mismatches" % (checked, how)) if args.full else how},
             "kernels_ms_per_step": {"assembler_stage": round(asm_sum / steps, 3), "schedule_kernel": round(acc["schedule_ms"] / steps, 3),
                                     "align_kernels": round(align_sum / steps, 3),
                                     "note": "HIP events per block, summed; blocks overlap, so the sum exceeds ms_per_step"},
@@ -640,16 +662,87 @@ def main():
                      "host_ms_per_step": {"h2d": round(acc["h2d_ms"] / steps, 2), "kernels": round(acc["kernel_ms"] / steps, 2),
                                           "d2h+compact": round(acc["d2h_ms"] / steps, 2)},
                      "gather_MB_per_step": round(gathered_bytes / steps / 1e6, 2)},
-            "algorithmic_bytes_per_locus": {"in": b_in / max(1, len(taken)), "ptr": b_ptr / max(1, len(taken)), "out": b_out / max(1, len(taken)),
-                                            "whole_path_GBps": round((b_in + b_ptr + b_out) / max(1, len(taken)) * n_loci * n_dev * steps / elapsed / 1e9, 2)},
             "dp_gcups": round(acc["dp_cells"] * (1 if proc_queue else world) / elapsed / 1e9, 2),
         }
+        if args.full:
+            if spanning:
+                b_in = sum(sum(len(x) for x in loci[i][0]) + len(loci[i][1]) + len(loci[i][2]) for i in taken)
+                b_ptr = b_out = 0
+                for i in taken:
+                    r = results[i]
+                    b_out += len(loci[i][0]) * 8
+                    for c, a in zip(r["contigs"], r["aligns"]):
+                        q = len(c["seq"])
+                        span = (len(loci[i][1]) + len(loci[i][2])) if a["is_uncut"] else (len(loci[i][1]) + len(loci[i][2]) - 400)
+                        b_ptr += (q + 1) * (span + 2)  # 1 B cells: the reference's own jump pointer matrix (GlobalJumpAligner.hpp:81-115)
+                        b_out += q + 2 * ((len(loci[i][0]) + 7) // 8) + 64
+                asm_bytes, align_bytes = sum(sum(len(x) for x in loci[i][0]) for i in taken) + b_out, b_ptr
+            else:
+                # (the stream's batches weighted by the timed steps each of them ran)
+                tot_w = max(1, sum(used)) if rotate else 1
+                b_in = b_ptr = b_out = asm_bytes = align_bytes = 0.0
+                for j, rj in enumerate(stream_res):
+                    w = (used[j] / tot_w) if rotate else (1.0 if j == 0 else 0.0)
+                    if w == 0.0 or rj is None:
+                        continue
+                    bj = stream[j][0]
+                    tk = taken if j == 0 else list(range(n_loci))
+                    bi, bp, bo, qb, wb = algorithmic_bytes_smallsv(bj, rj, tk)
+                    rin = sum(int(bj[1][bj[2][l + 1]] - bj[1][bj[2][l]]) for l in tk)
+                    b_in, b_ptr, b_out = b_in + w * bi, b_ptr + w * bp, b_out + w * bo
+                    asm_bytes, align_bytes = asm_bytes + w * (rin + bo), align_bytes + w * (qb + wb + bp)
+            # dominant kernel by HIP-event time summed over the timed region.  A launch = one block's kernel; the events of
+            # different blocks overlap on the device (that is the point of the block queue), each is timed on its own stream.
+            n_blocks = max(1, acc["n_blocks"])
+            if align_sum >= asm_sum:
+                dom, dom_bytes, dom_ms, dom_launches = align_name, align_bytes * steps, align_sum, n_blocks
+                dom_note = "per block: all E-bucket launches of the block (they run concurrently on side streams)"
+            else:
+                # the assembler stage of a block: graph_kernel -> contig_kernel (asm_lds.hpp; the general assemble_kernel for what they
+                # punt and under MANTA_AMD_ASM_PATH=general), timed by the library as ONE span of HIP events on the block's stream
+                dom = "assemble_kernel" if os.environ.get("MANTA_AMD_ASM_PATH") == "general" else "assembler_stage"
+                dom_bytes, dom_ms, dom_launches = asm_bytes * steps, asm_sum, n_blocks
+                dom_note = ("one launch per block" if dom == "assemble_kernel" else
+                            "per block: graph_kernel + contig_kernel (big piles: graph_big_kernel + repeat_big_kernel + contig_big_kernel, one round per word length) + assemble_kernel on what they hand back; one HIP-event "
+                            "span, rocprofv3 lists the kernels separately: their averages add up to avg_launch_ms")
+            avg_launch_ms = dom_ms / dom_launches
+            achieved = (dom_bytes / dom_launches) / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms > 0 else 0.0
+            # roofline.traffic is NOT measured in this run: it is the HBM-side byte count of the builder's own rocprofv3 --pmc passes
+            # (tools/profile_round.sh -> profiles/traffic*.json), quoted with its source and date
+            traffic, traffic_source = None, None
+            tpath = os.path.join(ROOT, "profiles", "traffic_spanning.json" if spanning else "traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    if tj.get("loci") == n_loci and tj.get("workload", "smallsv") == args.workload:
+                        traffic = tj.get(dom)
+                        traffic_source = "%s: %s, %s" % (os.path.relpath(tpath, ROOT), tj.get("source", "builder-run rocprofv3 --pmc passes"), tj.get("date", "round 2"))
+                    elif spanning and tj.get("workload") == "spanning" and tj.get("loci") and n_loci % tj["loci"] == 0 and tj.get(dom) is not None:
+                        # the spanning block TILES the distinct loci the counter passes ran on (2 048: the digest set; under the profiler larger
+                        # blocks run into the passes' time limit), so a launch's traffic is the counted bytes x the number of copies
+                        traffic = int(tj[dom] * (n_loci // tj["loci"]))
+                        traffic_source = ("%s: %s, %s; counted on %d loci, x %d: the block repeats those loci" %
+                                          (os.path.relpath(tpath, ROOT), tj.get("source", "builder-run rocprofv3 --pmc passes"), tj.get("date", ""), tj["loci"], n_loci // tj["loci"]))
+                except Exception:
+                    traffic = None
+            o["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": traffic_source,
+                             "algorithmic_bytes_per_launch": int(dom_bytes / dom_launches), "avg_launch_ms": round(avg_launch_ms, 3),
+                             "launches": dom_launches, "note": dom_note,
+                             # extra (not the contract's fraction): the counter traffic against what this chip delivers to 64-byte
+                             # random accesses (tools/microbench/gather_ceiling.hip, DESIGN.md 5.1: 3.36 TB/s) -- the bound the kernel sits on
+                             "sector_traffic": None if not traffic or avg_launch_ms <= 0 else
+                                               {"achieved_GBps": round(traffic / (avg_launch_ms * 1e-3) / 1e9, 1), "random_access_ceiling_GBps": 3360.0,
+                                                "frac": round(traffic / (avg_launch_ms * 1e-3) / 1e9 / 3360.0, 3),
+                                                "traffic_over_algorithmic": round(traffic / max(1.0, dom_bytes / dom_launches), 1)}}
+            o["algorithmic_bytes_per_locus"] = {"in": b_in / max(1, len(taken)), "ptr": b_ptr / max(1, len(taken)), "out": b_out / max(1, len(taken)),
+                                                "whole_path_GBps": round((b_in + b_ptr + b_out) / max(1, len(taken)) * n_loci * n_dev * steps / elapsed / 1e9, 2)}
         # ---- what the counters and the microbenchmarks say bounds the kernels (extra keys, quoted from profiles/ like roofline.traffic) ----
         # The contract's roofline object prices the dominant stage against its ALGORITHMIC bytes; this path is not bound by them.
         # Two figures that do describe the kernels: the aligner's real HBM rate (the back-pointer stream: counter bytes / this run's aligner
         # time) and, for the two assembler kernels, their use of the measured LDS ceilings (tools/microbench/lds_ceiling.hip).
         try:
-            if True:
+            if args.full:
                 tj = json.load(open(os.path.join(ROOT, "profiles", "traffic_spanning.json" if spanning else "traffic.json")))
                 at = tj.get("align_kernel<JUMP>" if spanning else "align_kernel<LARGE_INDEL>")
                 if at and tj.get("loci") and n_loci % tj["loci"] == 0 and align_sum > 0:
@@ -659,12 +752,12 @@ def main():
                                                     "achieved_GBps": round(gbps, 1), "peak": HBM_PEAK_GBPS, "frac": round(gbps / HBM_PEAK_GBPS, 4),
                                                     "note": "counter bytes of the builder's rocprofv3 --pmc passes (profiles/) over this run's aligner time: the back-pointer stream, written once, read along the traceback"}
             cpath = os.path.join(ROOT, "profiles", "ceilings.json")
-            if not spanning and os.path.exists(cpath):
+            if not spanning and args.full and os.path.exists(cpath):
                 o["roofline"]["issue"] = json.load(open(cpath))
         except Exception:
             pass
         # ---- device-resident kernel rate (extra key; round 1's headline): inputs in HBM, three kernels per step ----
-        if not spanning and world == 1 and not args.no_extras:
+        if not spanning and world == 1 and args.full and not args.no_extras:
             pipe = SmallSvBatch(lib, opts, SCORES, LARGE_INDEL)
             pipe.upload_packed(*batch)
             pipe.run()
@@ -682,7 +775,7 @@ def main():
                                 "kernels_ms": {k: round(v / nrun, 3) for k, v in ks.items()}}
             pipe.close()
         # ---- the same batch delivered as packed piles (what the read-pile builder emits from BAM records) ----
-        if not spanning and world == 1 and not args.no_extras:
+        if not spanning and world == 1 and args.full and not args.no_extras:
             from manta_amd._capi import pack_piles
             piles = pack_piles(batch[0], batch[1], batch[2])
             pin = piles if args.pageable else piles.pinned(lib)
@@ -710,7 +803,7 @@ def main():
         # ---- loci of very different sizes in one batch (extra key): read counts drawn log-uniformly from 3..1000, Manta's production word
         # lengths (IterativeAssemblerOptions.hpp:33-58: 41..76 step 5) -- the rate, and how the assembler stage routed the loci (the LDS
         # pipeline's two classes, what they handed back, what lies outside both envelopes)
-        if not spanning and world == 1 and not args.no_extras and not os.environ.get("MANTA_BENCH_NO_MIXED"):
+        if not spanning and world == 1 and args.full and not args.no_extras and not os.environ.get("MANTA_BENCH_NO_MIXED"):
             try:
                 from synth import mixed_shape_batch
                 n_mx = min(2048, max(8, n_loci))
@@ -760,11 +853,11 @@ def main():
         # ---- the config-4/5 shape (extra key, driver-visible): breakend loci, 200 reads x 250 bp, mixed word lengths, GlobalJumpAligner --
         # the same script with --workload spanning on 65 536 loci (2 048 distinct, tiled) in a process of its own (its own context and arenas), its line cut
         # down to what a reader of this line needs: rate, the assembler stage's roofline object, kernel times, the parity string
-        if (not spanning and world == 1 and not args.no_extras and not os.environ.get("MANTA_BENCH_NO_SPANNING")
+        if (not spanning and world == 1 and args.full and not args.no_extras and not os.environ.get("MANTA_BENCH_NO_SPANNING")
                 and os.path.abspath(lib.path) == os.path.join(ROOT, "manta_amd", "libmanta_amd.so")):
             try:
                 pr = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "spanning", "--loci", os.environ.get("MANTA_BENCH_SPANNING_LOCI", "65536"), "--steps", "2", "--warmup", "1",
-                                     "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=900)
+                                     "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=900)
                 rows = [l for l in pr.stdout.splitlines() if l.startswith("{")]
                 if pr.returncode == 0 and rows:
                     sp = json.loads(rows[-1])
@@ -772,7 +865,7 @@ def main():
                                      "loci": sp["config"]["loci_per_gpu"], "workload": sp["config"]["workload"], "parity": sp["config"]["parity"],
                                      "timed_region": sp["config"]["timed_region"], "roofline": sp["roofline"],
                                      "kernels_ms_per_step": sp["kernels_ms_per_step"], "algorithmic_bytes_per_locus": sp["algorithmic_bytes_per_locus"],
-                                     "dp_gcups": sp["dp_gcups"], "note": "python bench.py --workload spanning --loci %s --steps 2 --warmup 1, run by this script" % os.environ.get("MANTA_BENCH_SPANNING_LOCI", "65536")}
+                                     "dp_gcups": sp["dp_gcups"], "note": "python bench.py --workload spanning --loci %s --steps 2 --warmup 1 --full, run by this script" % os.environ.get("MANTA_BENCH_SPANNING_LOCI", "65536")}
                 else:
                     o["spanning"] = {"error": (pr.stderr or pr.stdout)[-300:]}
             except Exception as e:  # (an extra leg never takes the line down)
@@ -782,7 +875,7 @@ def main():
         # GenerateSVCandidates process would call, on 10 000 config-2 shaped complex candidates: reference and read
         # callbacks, packing, the device batch, the per-candidate host glue (tools/cpp/perf_refiner.cpp, built by __graft_entry__.build())
         exe = os.path.join(ROOT, "tools", "cpp", "perf_refiner")
-        if (not spanning and world == 1 and not args.no_extras and os.path.exists(exe)
+        if (not spanning and world == 1 and args.full and not args.no_extras and os.path.exists(exe)
                 and os.path.abspath(lib.path) == os.path.join(ROOT, "manta_amd", "libmanta_amd.so")):
             try:
                 pr = subprocess.run([exe, "10000", "0"], capture_output=True, text=True, timeout=600)
@@ -812,7 +905,7 @@ def main():
                         o["refiner_batch"]["real_types"] = real
                 except Exception as e:
                     o["refiner_batch"]["real_types"] = {"error": str(e)[-300:]}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cores = cores_available()
             kind, cpu = ("reference", RefLib()) if have_ref() else ("port", orc)
             if spanning:

@@ -5,9 +5,9 @@
 For every demo candidate: the records of each region query getBreakendReads makes (one per breakend and BAM; dumped field by field
 through the reference's own BAM layer, oracle/ref_bam_driver.cpp::ref_region_records), the reference windows the refiner fetches,
 and the pile the reference's UNMODIFIED SVCandidateAssembler::getBreakendReads builds from them (ref_breakend_pile).
-Writes tests/golden/read_class_demo.json.gz; tests/test_read_class.py replays the records through the restatement and the kernel."""
+Writes tests/golden/read_class_demo.json.xz (xz: the file stays under 1 MiB); tests/test_read_class.py replays the records through the restatement and the kernel."""
 import ctypes
-import gzip
+import lzma
 import json
 import os
 import subprocess
@@ -79,9 +79,9 @@ def main():
         print("%-36s pile %3d   records %s" % (c["name"], len(ref["reads"]), [len(regions[s["region"]]) for s in scans]), flush=True)
     blob = json.dumps(dict(source="reference demo BAMs through oracle/_ref/libmanta_ref_bam.so: ref_region_records (records), ref_breakend_pile "
                                   "(the unmodified getBreakendReads)", regions=regions, cases=cases)).encode()
-    with gzip.GzipFile(os.path.join(HERE, "read_class_demo.json.gz"), "wb", mtime=0) as f:
+    with lzma.open(os.path.join(HERE, "read_class_demo.json.xz"), "wb", preset=9 | lzma.PRESET_EXTREME) as f:
         f.write(blob)
-    print("bytes", len(blob), "->", os.path.getsize(os.path.join(HERE, "read_class_demo.json.gz")))
+    print("bytes", len(blob), "->", os.path.getsize(os.path.join(HERE, "read_class_demo.json.xz")))
 
 
 if __name__ == "__main__":

@@ -38,7 +38,7 @@ def check_cases(lib):
 
 
 def check_chain(lib, refiner):
-    """Product only, end to end: the decoded records of the demo BAMs' region queries (tests/golden/read_class_demo.json.gz) ->
+    """Product only, end to end: the decoded records of the demo BAMs' region queries (tests/golden/read_class_demo.json.xz) ->
     manta_read_piles_batch (read gathering on the device) -> those piles into the product refiner (device assemble + align through
     manta_smallsv_* / manta_spanning_*) -> candidateSV.vcf records; against the unmodified reference's refiner text and VCF records
     for the same candidates (tests/golden/demo_cases.json) and the published demo breakends.  Nothing of oracle/ in between."""

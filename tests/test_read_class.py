@@ -3,13 +3,14 @@
 
 Pinning chain:
   * the restatement (oracle/read_class_oracle.cpp) against the UNMODIFIED reference (oracle/_ref/libmanta_ref_bam.so: the real
-    SVCandidateAssembler.cpp + htsapi + htslib over BAM files): on the demo BAMs through tests/golden/read_class_demo.json.gz
+    SVCandidateAssembler.cpp + htsapi + htslib over BAM files): on the demo BAMs through tests/golden/read_class_demo.json.xz
     (records and reference piles stored by tests/golden/make_read_class_golden.py) and, where the _ref library is present, live on
     synthetic BAM files written for the purpose (SAM -> BAM with the redist htslib);
   * the kernel against the restatement on random record batches (decisions, pile positions, per-candidate results, pile text),
     and directly against the reference piles of the demo."""
 import ctypes
 import gzip
+import lzma
 import json
 import os
 import random
@@ -23,7 +24,7 @@ from manta_amd._capi import BatchOutput, read_class_options, small_sv_text
 from oracle_lib import asm_opts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = json.loads(gzip.open(os.path.join(ROOT, "tests", "golden", "read_class_demo.json.gz")).read())
+G = json.loads(lzma.open(os.path.join(ROOT, "tests", "golden", "read_class_demo.json.xz")).read())
 
 
 def demo_batch(cases):

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/prof_$TAG
 rm -rf $O && mkdir -p $O
 B="python $R/bench.py"
-timeout 400 $B > $O/bench_line.json 2> $O/bench.err
+timeout 400 $B --full > $O/bench_line.json 2> $O/bench.err
 timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B --steps 5 --warmup 1 --no-cpu-baseline --no-extras > $O/bench_under_rocprof.json 2> /dev/null
 P="--steps 1 --warmup 0 --no-cpu-baseline --no-extras"
 if [ -z "$PROFILE_LINES_ONLY" ]; then  # PROFILE_LINES_ONLY=1: bench line, kernel stats and the step trace only (the counter passes are kept)
@@ -24,7 +24,7 @@ fi
 # one plain kernel trace of the default step: every dispatch with its start / end (the gaps are the host turnarounds)
 timeout -s KILL 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_step -o t -- $B --steps 2 --warmup 1 --no-cpu-baseline --no-extras > /dev/null 2>&1
 if [ "$2" = "spanning" ]; then
-  timeout 600 $B --workload spanning --steps 2 --warmup 1 > $O/bench_spanning_line.json 2> $O/bench_spanning.err
+  timeout 600 $B --workload spanning --steps 2 --warmup 1 --full > $O/bench_spanning_line.json 2> $O/bench_spanning.err
   timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_spanning -o bench -- $B --workload spanning --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
   # (the config-5 shape's traffic counters: tools/gpu_r6_final.sh, on the 2 048 digest loci with the blocking upload -- a streamed upload under
   #  rocprofv3 --pmc never finishes: dispatches are serialised, the copy kernels wait for the assembler, which waits for its chunks)

@@ -524,7 +524,8 @@ struct AsmStage {
   int                   wavesPerCuCap = 0;  // > 0: leave wave slots free for another block's aligners (pipelined batch calls)
   bool                  useFast = false;  // the LDS pipeline (graph_kernel -> contig_kernel, asm_lds.hpp); what it does not cover goes to assemble_kernel
   int                   gridFast = 1;      // graph_kernel workgroups
-  int                   gridContig[manta_dev::LG_CLASSES] = {0, 0, 0, 0};  // contig_kernel workgroups per LDS size class
+  int                   gridContig[manta_dev::LG_CLASSES] = {0, 0, 0, 0};  // contig_kernel workgroups (contig_pool_kernel: waves) per LDS size class
+  bool                  contigPool = false;  // the small class on contig_pool_kernel
   uint32_t              classBytes[manta_dev::LG_CLASSES] = {0, 0, 0, 0};
   uint64_t              lgArenaCap = 0, cwsStride = 0;
   std::vector<uint32_t> fastIds, genIds;  // cost-ordered work lists of the two paths
@@ -545,7 +546,7 @@ struct AsmStage {
   int                   gridRepeat = 0;    // repeat_big_kernel wavefronts
   uint64_t              pseudoArenaDw = 0, rwsStride = 0;
   DevBuf                bLgIter, bLgPseudo, bLgNext, bLgCyc, bLgRounds, bRws, bGws;
-  DevBuf                bPunt, bLgArena, bLgOff, bLgClassIds, bLgCnt, bCws;
+  DevBuf                bPunt, bLgArena, bLgOff, bLgClassIds, bLgCnt, bCws, bLgBins;
   uint32_t*             dPunt = nullptr;   // the general kernel's list: genIds, then the loci the LDS pipeline punted
   // packed piles of the uploaded batch (manta_packed_piles_t), device side; dPlCodes == nullptr: 1 byte per base input
   DevBuf                bPlCodes, bPlMask, bPlLen, bPlCodeOff, bPlMaskOff;
@@ -743,7 +744,9 @@ struct AsmStage {
     if (useFast) {
       using namespace manta_dev;
       // graph_kernel: two workgroups of LG_WAVES wavefronts per CU (LG_BUDGET bytes of LDS each).  contig_kernel: one launch per
-      // LDS size class; a class of B bytes runs floor(160 KB / B) single-wave workgroups per CU (asked of the runtime).
+      // LDS size class; a class of B bytes runs floor(160 KB / B) single-wave workgroups per CU (asked of the runtime), except the small
+      // class on contig_pool_kernel: one workgroup of CK_POOL_WAVES waves per CU.  Every wave has its own HBM workspace (cwsStride bytes,
+      // ~170 KB), so the wave counts are held to wsBudget as well.
       gridFast = int(std::max<uint64_t>(1, std::min<uint64_t>(fastIds.size(), uint64_t(ctx->cuCount) * (163840 / LG_BUDGET))));
       static const uint32_t kClassDefault[LG_CLASSES] = {20480, 54272, 0, 0};  // 8 / 3 workgroups per CU (measured: every further class costs a launch tail)
       for (unsigned c = 0; c < LG_CLASSES; ++c) classBytes[c] = kClassDefault[c];
@@ -760,18 +763,35 @@ struct AsmStage {
         }
         for (; c < LG_CLASSES; ++c) classBytes[c] = 0;
       }
+      // The small class (class 0) runs on contig_pool_kernel (asm_contig.hpp: the workgroup's LDS is a pool the waves take their loci's
+      // bytes from) whenever one of its loci fits an empty pool; MANTA_AMD_NO_CONTIG_POOL (A/B runs) keeps it on contig_kernel.
+      contigPool = classBytes[0] && classBytes[0] <= CK_POOL_BYTES - CK_POOL_HDR && !std::getenv("MANTA_AMD_NO_CONTIG_POOL");
       int maxGrid = 1;
       for (unsigned c = 0; c < LG_CLASSES; ++c) {
         gridContig[c] = 0;
         if (!classBytes[c]) continue;
+        if (c == 0 && contigPool) {
+          const int      perCu = std::max(1, rt::blocksPerCu(contig_pool_kernel, 64 * int(CK_POOL_WAVES), CK_POOL_BYTES, int(163840 / CK_POOL_BYTES)));
+          const uint64_t wgs   = std::min<uint64_t>({(fastIds.size() + CK_POOL_WAVES - 1) / CK_POOL_WAVES, uint64_t(ctx->cuCount) * perCu,
+                                                     wsBudget / (uint64_t(CK_POOL_WAVES) * ckWorkspaceLayout().total)});
+          gridContig[c]        = int(CK_POOL_WAVES * std::max<uint64_t>(1, wgs));
+          maxGrid              = std::max(maxGrid, gridContig[c]);
+          continue;
+        }
         static const int wgCap = std::getenv("MANTA_AMD_CONTIG_WG_CAP") ? std::atoi(std::getenv("MANTA_AMD_CONTIG_WG_CAP")) : 8;  // experiments
         const int perCu = std::max(1, std::min(wgCap, rt::blocksPerCu(contig_kernel, 64, classBytes[c], int(163840 / classBytes[c]))));
-        gridContig[c]   = int(std::max<uint64_t>(1, std::min<uint64_t>(fastIds.size(), uint64_t(ctx->cuCount) * perCu)));
+        gridContig[c]   = int(std::max<uint64_t>(1, std::min<uint64_t>({fastIds.size(), uint64_t(ctx->cuCount) * perCu, wsBudget / ckWorkspaceLayout().total})));
         maxGrid         = std::max(maxGrid, gridContig[c]);
       }
       if (std::getenv("MANTA_AMD_DEBUG"))
-        for (unsigned c = 0; c < LG_CLASSES; ++c)
-          if (classBytes[c]) std::fprintf(stderr, "manta_amd: contig_kernel class %u: %u bytes of LDS, %d workgroups (%d per CU by the runtime's count)\n", c, classBytes[c], gridContig[c], rt::blocksPerCu(contig_kernel, 64, classBytes[c], -1));
+        for (unsigned c = 0; c < LG_CLASSES; ++c) {
+          if (!classBytes[c]) continue;
+          if (c == 0 && contigPool)
+            std::fprintf(stderr, "manta_amd: contig_pool_kernel class 0: up to %u bytes per locus from pools of %u bytes, %d waves in workgroups of %u (%d per CU by the runtime's count)\n",
+                         classBytes[c], CK_POOL_BYTES, gridContig[c], CK_POOL_WAVES, rt::blocksPerCu(contig_pool_kernel, 64 * int(CK_POOL_WAVES), CK_POOL_BYTES, -1));
+          else
+            std::fprintf(stderr, "manta_amd: contig_kernel class %u: %u bytes of LDS, %d workgroups (%d per CU by the runtime's count)\n", c, classBytes[c], gridContig[c], rt::blocksPerCu(contig_kernel, 64, classBytes[c], -1));
+        }
       cwsStride  = ckWorkspaceLayout().total;
       // the big class: one graph workgroup per CU; contig_big_kernel in two LDS classes (two loci / one locus per CU)
       gridBig = int(std::max<uint64_t>(1, std::min<uint64_t>(bigIds.size(), uint64_t(ctx->cuCount))));
@@ -1092,6 +1112,7 @@ struct AsmStage {
       (void)bLgArena.as<uint8_t>(lgArenaCap + 64);
       (void)bLgOff.as<uint64_t>(nLoci);
       (void)bLgClassIds.as<uint32_t>(uint64_t(manta_dev::LG_CLASSES) * std::max<size_t>(1, fastIds.size()));
+      if (contigPool) (void)bLgBins.as<uint32_t>(manta_dev::CK_BIN_IDS + uint64_t(manta_dev::CK_BINS) * fastIds.size());
       (void)bLgCnt.as<uint64_t>(16);
       (void)bCws.as<uint8_t>(cwsStride * uint64_t(maxGrid));
       if (!bigIds.empty()) {
@@ -1220,6 +1241,12 @@ struct AsmStage {
       for (unsigned c = 0; c < LG_CLASSES; ++c) maxGrid = std::max(maxGrid, gridContig[c]);
       A.G.cws        = bCws.as<uint8_t>(cwsStride * uint64_t(maxGrid));
       A.G.cws_stride = cwsStride;
+      // the pool takes the small class by cost bins (largest graphs first); the bins' counters are zeroed here, their lists filled by graph_kernel
+      A.G.cost_bins = nullptr;
+      if (contigPool && !fastIds.empty()) {
+        A.G.cost_bins = bLgBins.as<uint32_t>(CK_BIN_IDS + uint64_t(CK_BINS) * fastIds.size());
+        rt::dzero(A.G.cost_bins, sizeof(uint32_t) * CK_BIN_IDS);
+      }
       A.G.round = A.G.last_round = 0;
       A.G.iter        = nullptr;  // (the big class' rounds set these)
       A.G.parena      = nullptr;
@@ -1262,13 +1289,17 @@ struct AsmStage {
           A.G.cls       = c;
           A.P.counter   = reinterpret_cast<uint32_t*>(dLg + 3) + c;
           A.P.lds_bytes = classBytes[c];
-          rt::launchSingle(contig_kernel, gridContig[c], classBytes[c], A);
+          if (c == 0 && contigPool)
+            rt::launchWG(contig_pool_kernel, gridContig[c] / int(CK_POOL_WAVES), int(CK_POOL_WAVES), CK_POOL_BYTES, A);
+          else
+            rt::launchSingle(contig_kernel, gridContig[c], classBytes[c], A);
         }
       };
       firstRoundHookRan = false;
       if (!bigIds.empty()) {
         // the big class: its own work list (behind the small class' in dOrder), class lists and counters; slabs and punts shared
         LgArgs B         = A;
+        B.G.cost_bins    = nullptr;
         B.P.n_loci       = uint32_t(bigIds.size());
         B.P.locus_ids    = dOrder + fastIds.size();
         B.P.counter      = reinterpret_cast<uint32_t*>(dLg + 7);
@@ -1586,6 +1617,16 @@ struct AsmStage {
       std::fprintf(stderr, "manta_amd: LDS assembler pipeline: %zu + %zu (big class) loci, %u handed to the general kernel (+ %zu outside its envelope); %u + %u graphs came "
                            "with a proof of acyclicity, %u + %u reads re-anchored; big class: %u / %u loci in its two contig LDS classes\n", fastIds.size(), bigIds.size(),
                    ldsFallbacks, genIds.size(), st[0], stBig[0], st[1], stBig[1], clsBig[0], clsBig[1]);
+      if (contigPool && !fastIds.empty()) {
+        // contig_pool_kernel: one pool per CU, so the loci resident in a pool when a wave takes its share are the CU's
+        uint32_t bins[manta_dev::CK_BIN_IDS];
+        rt::d2h(bins, bLgBins.as<uint32_t>(manta_dev::CK_BIN_IDS + uint64_t(manta_dev::CK_BINS) * fastIds.size()), sizeof(bins));
+        const uint32_t* ps = bins + manta_dev::CK_BIN_STAT;
+        std::fprintf(stderr, "manta_amd: contig_pool_kernel: %u shares taken, %.2f loci resident per CU on average at a take, %u takes waited for room (%u polls); "
+                             "loci by cost bin (largest first):", ps[0], ps[0] ? double(ps[1]) / ps[0] : 0.0, ps[2], ps[3]);
+        for (unsigned b = 0; b < manta_dev::CK_BINS; ++b) std::fprintf(stderr, " %u", bins[b]);
+        std::fprintf(stderr, "\n");
+      }
       if (!bigIds.empty())
         std::fprintf(stderr, "manta_amd: big class, %u word-length rounds; handed back: %u envelope, %u table / set pool, %u words / side tables / class, %u slab arena, %u by "
                              "repeat_big_kernel, %u by contig_big_kernel, %u pseudo arena, %u out of rounds\n", bigRounds, stBig[2], stBig[3], stBig[4], stBig[5], stBig[6],

@@ -1407,6 +1407,126 @@ WV_KERNEL_SINGLE WV_WAVES_PER_SIMD(2) void contig_kernel(const LgArgs A)
   contigKernelBody<LgS>(A);
 }
 #endif
+
+// contig_pool_kernel: the small class (class 0) on workgroups of CK_POOL_WAVES independent waves whose CK_POOL_BYTES of LDS are one
+// pool.  A wave takes its locus' ckNeed bytes (the slab header's `need`) from the pool, runs the locus, and gives them back.  With a
+// fixed share per wave a CU holds floor(160 KB / class bytes) loci whatever their size; from a pool it holds as many as their real sizes
+// allow (12.7-18.9 KB for a config-2 locus, 20 KB at most), up to the workgroup's 12 waves.
+//   The pool's first CK_POOL_HDR bytes: u32 lock, u32[CK_POOL_WAVES] each wave's share {start, end} in 16-byte units (start == end:
+// none).  A wave changes its share only under the lock; allocation is first fit over the candidates "pool start" and "end of a share".
+//   Nothing can deadlock: a wave that finds no room holds no share while it waits, every share is given back when its locus is done
+// (no wave waits for anything while it holds one), and any single locus of the class fits the empty pool (the host launches this
+// kernel only if the class' bytes do), so at the latest when the other waves' loci are done the waiting wave's locus fits.
+static const unsigned CK_POOL_WAVES = 12;
+static const unsigned CK_POOL_BYTES = 163840;  // one workgroup per CU: 3 waves per SIMD (two 6-wave workgroups did not share a CU)
+static const unsigned CK_POOL_HDR   = 64;
+static_assert(4 * (1 + CK_POOL_WAVES) <= CK_POOL_HDR && (CK_POOL_BYTES - CK_POOL_HDR) / 16 < 65536, "pool header");
+
+/// `units` 16-byte units of the pool for wave `w` (waits for room); returns the byte offset of the share.  `stat` (nullptr: none): the
+/// CK_BIN_STAT counters of LgParams::cost_bins
+WV_DEV unsigned ckPoolTake(char* pool, const unsigned w, const unsigned units, uint32_t* stat)
+{
+  uint32_t*      lock  = reinterpret_cast<uint32_t*>(pool);
+  uint32_t*      share = lock + 1;
+  const unsigned lane  = unsigned(wv::lane());
+  const unsigned capU  = (CK_POOL_BYTES - CK_POOL_HDR) / 16;
+  unsigned       polls = 0;
+  while (true) {
+    ++polls;
+    unsigned got = 0;
+    if (lane == 0) got = (wv::atomic_cas(lock, 0u, 1u) == 0u) ? 1u : 0u;
+    if (wv::first(got)) {
+      wv::fence_wg();
+      // lane 0: the pool's start; lane 1 + v: the end of wave v's share
+      unsigned s = 0;
+      if (lane >= 1 && lane <= CK_POOL_WAVES) s = wv::atomic_load(&share[lane - 1]) >> 16;
+      bool ok = lane <= CK_POOL_WAVES && s + units <= capU;
+      for (unsigned v = 0; v < CK_POOL_WAVES; ++v) {
+        const unsigned e = wv::atomic_load(&share[v]), a = e & 0xffffu, b = e >> 16;
+        if (a < b && s < b && a < s + units) ok = false;
+      }
+      const uint64_t m  = wv::ballot(ok);
+      const unsigned at = m ? wv::readlane(s, wv::ctz(m)) : 0u;
+      if (m && lane == 0) wv::atomic_store(&share[w], at | ((at + units) << 16));
+      // (lane v < CK_POOL_WAVES: does wave v hold a share now -- the loci resident in this pool, this one included)
+      const unsigned e        = (lane < CK_POOL_WAVES) ? wv::atomic_load(&share[lane]) : 0u;
+      const bool     held     = (e & 0xffffu) < (e >> 16);
+      const unsigned resident = unsigned(wv::popc(wv::ballot(held)));
+      wv::fence_wg();
+      if (lane == 0) wv::atomic_exch(lock, 0u);
+      if (m) {
+        if (stat && lane == 0) {
+          wv::atomic_add(&stat[0], 1u);
+          wv::atomic_add(&stat[1], resident);
+          if (polls > 1) wv::atomic_add(&stat[2], 1u);
+          wv::atomic_add(&stat[3], polls);
+        }
+        return CK_POOL_HDR + 16 * at;
+      }
+    }
+    wv::sleep();  // (a locus takes ~10^6 clocks: a waiting wave polls rarely and leaves the LDS and the issue slots to the others)
+  }
+}
+
+template <class C>
+WV_DEV void contigPoolBody(const LgArgs& A)
+{
+  const AsmParams& P    = A.P;
+  const LgParams&  G    = A.G;
+  const unsigned   w    = unsigned(wv::wave_in_wg());
+  uint8_t*         ws   = G.cws + (uint64_t(wv::block_single()) * unsigned(wv::wg_waves()) + w) * G.cws_stride;
+  char*            pool = wv::lds_single();
+  if (w == 0 && wv::lane() <= int(CK_POOL_WAVES)) reinterpret_cast<uint32_t*>(pool)[wv::lane()] = 0u;  // lock, shares
+  wv::wg_barrier();
+  const unsigned  nLoci = wv::first(wv::atomic_load(&G.class_count[G.cls]));
+  const uint32_t* ids   = G.class_ids + size_t(G.cls) * G.class_stride;
+  const unsigned  capU  = (P.lds_bytes + 15) / 16;
+  // with cost bins (graph_kernel filed class 0 by ckNeed): lane b < CK_BINS holds bin b's first slot and its length, bin 0 first
+  const unsigned lane   = unsigned(wv::lane());
+  unsigned       binLen = 0, binAt = 0;
+  if (G.cost_bins) {
+    binLen = (lane < CK_BINS) ? wv::atomic_load(&G.cost_bins[lane]) : 0u;
+    binAt  = binLen;
+    for (int off = 1; off < 64; off <<= 1) {
+      const unsigned o = wv::shfl(binAt, int(lane) - off);
+      if (int(lane) >= off) binAt += o;
+    }
+    binAt -= binLen;
+  }
+  while (true) {
+    unsigned slot = 0;
+    if (lane == 0) slot = wv::atomic_add(P.counter, 1u);
+    slot = wv::first(slot);
+    if (slot >= nLoci) break;
+    unsigned locus;
+    if (G.cost_bins) {
+      const uint64_t inBin = wv::ballot(lane < CK_BINS && slot >= binAt && slot < binAt + binLen);
+      const unsigned b     = unsigned(wv::ctz(inBin));  // (the bins' lengths add up to nLoci: every class-0 locus is in one)
+      locus                = G.cost_bins[CK_BIN_IDS + size_t(b) * G.class_stride + (slot - wv::readlane(binAt, int(b)))];
+    } else {
+      locus = ids[slot];
+    }
+    // (a need above the class' bytes cannot be filed here; load() would punt it before it touches LDS)
+    const LgHdr*   gh    = reinterpret_cast<const LgHdr*>(G.arena + G.slab_off[locus]);
+    const unsigned needU = (wv::first(gh->need) + 15) / 16;
+    const unsigned units = (needU < capU) ? needU : capU;
+    char*          lds   = pool + ckPoolTake(pool, w, units, G.cost_bins ? G.cost_bins + CK_BIN_STAT : nullptr);
+    LdsContig<C>   c(P, G, lds, ws);
+    const int      rc = c.run(locus);
+    wv::sync();
+    if (wv::lane() == 0) wv::atomic_store(reinterpret_cast<uint32_t*>(pool) + 1 + w, 0u);  // the share goes back
+    if (rc == CK_PUNT && wv::lane() == 0) P.punt_ids[wv::atomic_add(P.punt_count, 1u)] = locus;
+    wv::sync();
+  }
+}
+#if !MANTA_TU_DEFINES(MANTA_TU_CONTIG)
+WV_KERNEL_WG(CK_POOL_WAVES) WV_WAVES_PER_SIMD(3) void contig_pool_kernel(const LgArgs A);
+#else
+WV_KERNEL_WG(CK_POOL_WAVES) WV_WAVES_PER_SIMD(3) void contig_pool_kernel(const LgArgs A)
+{
+  contigPoolBody<LgS>(A);
+}
+#endif
 /// the big class (asm_lds_big.hpp): read sets of four qwords, 13-bit ids; one or two loci per CU
 #if !MANTA_TU_DEFINES(MANTA_TU_CONTIG)
 WV_KERNEL_SINGLE WV_WAVES_PER_SIMD(1) void contig_big_kernel(const LgArgs A);

@@ -43,6 +43,14 @@ static const unsigned LG_BUDGET    = 81920;  // its LDS: two workgroups per CU
 static const unsigned LG_SIB_CAP   = 32;     // words without a predecessor that have siblings (side table)
 static const unsigned LG_OVF_CAP   = 32;     // words with more than two successors / predecessors (side tables)
 static const unsigned LG_CLASSES   = 4;      // LDS size classes of contig_kernel (one launch each)
+// The small class' list in cost bins (LgParams::cost_bins, u32): [0, CK_BINS) loci per bin, [CK_BINS, CK_BINS + 4) contig_pool_kernel's
+// counters (shares taken, loci resident summed over the takes, takes that waited, polls), from CK_BIN_IDS on the bins' lists of
+// class_stride ids each.  Bin b holds the graphs with b KB less than the class' bytes in front of their ckNeed (the last bin: the rest);
+// ckNeed grows with the words and their read sets, which is what a locus' walks cost, so the pool takes the big ones first and the
+// launch ends on small ones.
+static const unsigned CK_BINS     = 8;
+static const unsigned CK_BIN_STAT = CK_BINS;
+static const unsigned CK_BIN_IDS  = 16;
 
 // graph_kernel LDS map (bytes)
 static const unsigned LG_OFF_HDR   = 0;                          // u32[64] header words, u16[128] byte offset of a read in the staged pile
@@ -360,6 +368,7 @@ struct LgParams {
   uint32_t            flags;       ///< LG_FLAG_*
   uint32_t*           stats;       ///< [0] loci whose graph came with a proof of acyclicity, [1] reads re-anchored by readOffsets' second pass
   uint8_t*            cws;         ///< contig_kernel workspaces
+  uint32_t*           cost_bins;   ///< nullptr, or the small class' list by cost (contig_pool_kernel, largest graphs first): see CK_BIN_*
   uint64_t            cws_stride;
   // ---- the big class' word-length rounds (asm_lds_big.hpp / asm_repeat_big.hpp); iter == nullptr: one round, repeat hits are handed back
   uint32_t            round;       ///< this launch's round (0: the first word length)
@@ -1544,7 +1553,14 @@ struct LdsGraph {
       h.nPseudo = h.cyclic = h.nCore = 0;
       *reinterpret_cast<LgHdr*>(slab) = h;
       G.slab_off[locus]               = off;
-      G.class_ids[size_t(cls) * G.class_stride + wv::atomic_add(&G.class_count[cls], 1u)] = locus;
+      const unsigned slot = wv::atomic_add(&G.class_count[cls], 1u);
+      if (cls == 0 && G.cost_bins) {
+        const unsigned b = (G.class_bytes[0] - need) / 1024u;
+        const unsigned c = (b < CK_BINS) ? b : CK_BINS - 1;
+        G.cost_bins[CK_BIN_IDS + size_t(c) * G.class_stride + wv::atomic_add(&G.cost_bins[c], 1u)] = locus;
+      } else {
+        G.class_ids[size_t(cls) * G.class_stride + slot] = locus;
+      }
     }
     tick(4, 7);
     return true;

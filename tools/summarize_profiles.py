@@ -73,7 +73,7 @@ agg = {}
 for k, v in per.items():
     if k.startswith("align_kernel<1") or k.startswith("align_pair"):
         name = "align_kernel<LARGE_INDEL>"  # (the E-bucket launches of a block, packed pairs or not, together)
-    elif k.startswith("graph_kernel") or k.startswith("contig_kernel") or k.startswith("assemble_kernel"):
+    elif k.startswith("graph_kernel") or k.startswith("contig_kernel") or k.startswith("contig_pool_kernel") or k.startswith("assemble_kernel"):
         name = "assembler_stage"  # graph_kernel + contig_kernel (+ the general kernel's launch for punted loci): what bench.py times as the assembler
     else:
         name = k

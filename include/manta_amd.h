@@ -51,26 +51,33 @@ const char* manta_ctx_device_name(const manta_ctx_t* ctx);
  *   GlobalAligner<int>::align            alignment/GlobalAligner.hpp:36-46   (kind MANTA_ALIGNER_GLOBAL)
  *   GlobalLargeIndelAligner<int>::align  alignment/GlobalLargeIndelAligner.hpp:39-54 (MANTA_ALIGNER_LARGE_INDEL)
  *   GlobalJumpAligner<int>::align        alignment/GlobalJumpAligner.hpp:36-53       (MANTA_ALIGNER_JUMP)
- * called at SVCandidateAssemblyRefiner.cpp:933, 1668, 1706, 2032.
+ *   GlobalJumpIntronAligner<int>::align  alignment/GlobalJumpIntronAligner.hpp:46-57 (MANTA_ALIGNER_JUMP_INTRON, RNA mode;
+ *                                        through manta_align_intron_batch only)
+ * called at SVCandidateAssemblyRefiner.cpp:933, 1621, 1668, 1706, 2032.
  * ---------------------------------------------------------------------------------------------------- */
-enum { MANTA_ALIGNER_GLOBAL = 0, MANTA_ALIGNER_LARGE_INDEL = 1, MANTA_ALIGNER_JUMP = 2 };
+enum { MANTA_ALIGNER_GLOBAL = 0, MANTA_ALIGNER_LARGE_INDEL = 1, MANTA_ALIGNER_JUMP = 2, MANTA_ALIGNER_JUMP_INTRON = 3 };
 
 /* alignment/AlignmentScores.hpp:23-57 */
 typedef struct {
   int32_t match, mismatch, open, extend, off_edge;
-  int32_t is_allow_edge_insertion; /* must be 0 for MANTA_ALIGNER_JUMP (GlobalJumpAligner.hpp:41-42) */
+  int32_t is_allow_edge_insertion; /* must be 0 for MANTA_ALIGNER_JUMP (GlobalJumpAligner.hpp:41-42) and MANTA_ALIGNER_JUMP_INTRON */
 } manta_align_scores_t;
 
 /* one query/reference(s) problem; offsets index the caller's sequence arena */
 typedef struct {
   uint64_t query_off;
   uint64_t ref1_off;
-  uint64_t ref2_off; /* MANTA_ALIGNER_JUMP only */
+  uint64_t ref2_off; /* MANTA_ALIGNER_JUMP and MANTA_ALIGNER_JUMP_INTRON only */
   uint32_t query_len;
   uint32_t ref1_len;
   uint32_t ref2_len;
-  uint32_t reserved;
+  uint32_t reserved; /* manta_align_intron_batch: MANTA_INTRON_* flags of the task; not read by manta_align_batch */
 } manta_align_task_t;
+
+/* manta_align_task_t.reserved for manta_align_intron_batch: the ref1Fw / ref2Fw / isStranded arguments of
+ * GlobalJumpIntronAligner::align.  A stranded task accepts the splice motifs of each reference's own strand (GT..AG forward,
+ * CT..AC reverse), an unstranded one those of both strands. */
+enum { MANTA_INTRON_REF1_FW = 1, MANTA_INTRON_REF2_FW = 2, MANTA_INTRON_STRANDED = 4 };
 
 /* CIGAR segments are BAM-packed: (length << 4) | op, op = 0 M,1 I,2 D,3 N,4 S,5 H,6 P,7 '=',8 'X'
  * (ALIGNPATH::align_t, blt_util/align_path.hpp:35-62).  Paths are always in '='/'X' form, as the reference's
@@ -93,6 +100,19 @@ int manta_align_batch(
     manta_ctx_t* ctx, int kind, const manta_align_scores_t* scores, int32_t extra_score, uint32_t n_tasks,
     const manta_align_task_t* tasks, const uint8_t* seq_arena, uint64_t seq_arena_bytes,
     manta_align_result_t* results, uint32_t* cigar_arena, uint64_t cigar_arena_cap, uint64_t* cigar_arena_used);
+
+/* GlobalJumpIntronAligner<int>(scores, jump_score, intron_open_score, intron_off_edge_score).align(query, ref1, ref2, ref1Fw, ref2Fw,
+ * isStranded) for every task; the three booleans are the MANTA_INTRON_* bits of the task's `reserved` word (any other bit:
+ * MANTA_E_INVALID_ARG).  scores->is_allow_edge_insertion must be 0 (the reference's constructor asserts it).  An empty query, ref1
+ * or ref2 gives that task MANTA_E_EMPTY_SEQ, as for MANTA_ALIGNER_JUMP.  Results as for MANTA_ALIGNER_JUMP; introns are 'N' segments.
+ * cigar arena: 2*query_len+8 segments per task still suffice -- the intron state is entered only from a match and left only to a
+ * match, so like a deletion an 'N' segment stands between two segments that consume query bases (or at an end of the path).
+ * (manta_align_batch refuses kind MANTA_ALIGNER_JUMP_INTRON: it has no room for the two intron scores.) */
+int manta_align_intron_batch(
+    manta_ctx_t* ctx, const manta_align_scores_t* scores, int32_t jump_score, int32_t intron_open_score,
+    int32_t intron_off_edge_score, uint32_t n_tasks, const manta_align_task_t* tasks, const uint8_t* seq_arena,
+    uint64_t seq_arena_bytes, manta_align_result_t* results, uint32_t* cigar_arena, uint64_t cigar_arena_cap,
+    uint64_t* cigar_arena_used);
 
 /* ------------------------------------------------------------------------------------------------------
  * Assembler.  Replaces

@@ -47,6 +47,9 @@ class AlignTask(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+INTRON_REF1_FW, INTRON_REF2_FW, INTRON_STRANDED = 1, 2, 4  # manta_align_task_t.reserved for manta_align_intron_batch
+
+
 class AlignResult(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("score", ctypes.c_int32), ("is_jumped", ctypes.c_int32),
                 ("begin_pos1", ctypes.c_int32), ("begin_pos2", ctypes.c_int32), ("jump_insert_size", ctypes.c_uint32),
@@ -228,6 +231,22 @@ class Lib:
     # ------------------------------------------------------------------ aligners
     def align_batch(self, kind, scores, extra, problems, strict=True):
         """problems: list of (query, ref1[, ref2]) byte strings.  Returns list of dicts (per-task status kept)."""
+        return self._align_call(problems, strict, lambda sc, *rest: self.lib.manta_align_batch(self.ctx, kind, ctypes.byref(sc), extra, *rest),
+                                scores)
+
+    def align_intron_batch(self, scores, jump, intron_open, intron_off_edge, problems, strict=True):
+        """GlobalJumpIntronAligner (RNA mode).  problems: list of (query, ref1, ref2, ref1_fw, ref2_fw, stranded).  Returns list of dicts as
+        align_batch does; introns are 'N' segments of the cigars."""
+        f = self.lib.manta_align_intron_batch
+        f.restype = ctypes.c_int
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p,
+                      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        flags = [(INTRON_REF1_FW if p[3] else 0) | (INTRON_REF2_FW if p[4] else 0) | (INTRON_STRANDED if p[5] else 0) for p in problems]
+        return self._align_call(problems, strict, lambda sc, n, tasks, *rest: f(self.ctx, ctypes.byref(sc), jump, intron_open, intron_off_edge,
+                                                                                 n, ctypes.cast(tasks, ctypes.c_void_p), *rest),
+                                scores, flags, cast=True)
+
+    def _align_call(self, problems, strict, call, scores, flags=None, cast=False):
         arena = bytearray()
         tasks = (AlignTask * max(1, len(problems)))()
         for i, pr in enumerate(problems):
@@ -240,15 +259,17 @@ class Lib:
             arena += r1
             t.ref2_off, t.ref2_len = len(arena), len(r2)
             arena += r2
+            if flags is not None:
+                t.reserved = flags[i]
         arena_np = np.frombuffer(bytes(arena) + b"\0", dtype=np.uint8)
         res = (AlignResult * max(1, len(problems)))()
         cap = sum(2 * len(_b(p[0])) + 8 for p in problems) + 8
         cig = np.zeros(cap, dtype=np.uint32)
         used = ctypes.c_uint64(0)
         sc = AlignScores(*scores)
-        rc = self.lib.manta_align_batch(self.ctx, kind, ctypes.byref(sc), extra, len(problems), tasks,
-                                        arena_np.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(len(arena)), res,
-                                        cig.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(cap), ctypes.byref(used))
+        rc = call(sc, len(problems), tasks, arena_np.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(len(arena)),
+                  ctypes.cast(res, ctypes.c_void_p) if cast else res, cig.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(cap),
+                  ctypes.cast(ctypes.pointer(used), ctypes.c_void_p) if cast else ctypes.byref(used))
         self._check(rc, allow=() if strict else (-4, -5))
         out = []
         for i in range(len(problems)):

@@ -19,7 +19,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-I
 HOST_TU = 1
 KERNEL_TUS = {
     2: "asm", 3: "asm_generic", 4: "graph", 5: "graph_big", 6: "contig", 7: "repeat", 8: "align0", 9: "align1", 10: "align2",
-    11: "align_pair", 12: "jump_pair", 13: "glue",
+    11: "align_pair", 12: "jump_pair", 13: "glue", 14: "align3",
 }
 HOST_SOURCES = ["api.cpp", "api_batch.cpp", "api_reads.cpp"]
 

@@ -2,6 +2,7 @@
 //   KIND 0  GlobalAligner            (alignment/GlobalAlignerImpl.hpp:29-181)            3 states
 //   KIND 1  GlobalLargeIndelAligner  (alignment/GlobalLargeIndelAlignerImpl.hpp:35-225)  5 states
 //   KIND 2  GlobalJumpAligner        (alignment/GlobalJumpAlignerImpl.hpp:33-333)        4 states, two references
+//   KIND 3  GlobalJumpIntronAligner  (alignment/GlobalJumpIntronAlignerImpl.hpp:57-415)  5 states, two references, splice motifs
 // plus their tracebacks (SingleRefAlignerSharedImpl.hpp:75-168, JumpAlignerBaseImpl.hpp:86-242) and the '='/'X'
 // expansion (blt_util/align_path_impl.hpp:33-72).  Paths are relative to /root/reference/src/c++/lib.
 //
@@ -30,7 +31,7 @@
 
 namespace manta_dev {
 
-enum { ST_MATCH = 0, ST_DELETE = 1, ST_INSERT = 2, ST_JUMP = 3, ST_JUMPINS = 4 };  // alignment/Alignment.hpp:47-56
+enum { ST_MATCH = 0, ST_DELETE = 1, ST_INSERT = 2, ST_JUMP = 3, ST_JUMPINS = 4, ST_SPLICE = 4 };  // alignment/Alignment.hpp:47-56
 // CIGAR ops, BAM numbering (type in low 4 bits, length << 4)
 enum { OP_M = 0, OP_I = 1, OP_D = 2, OP_N = 3, OP_S = 4, OP_H = 5, OP_P = 6, OP_EQ = 7, OP_X = 8, OP_NONE = 15 };
 
@@ -64,6 +65,9 @@ struct AlignParams {
   uint8_t*            ptr_ws;   ///< back-pointer slabs, one per workgroup
   uint64_t            ptr_ws_stride;
   int32_t             match, mismatch, open, extend, off_edge, allow_edge_ins, extra;
+  // KIND 3 only: the intron scores and one word of flags per task (bit 0 ref1Fw, bit 1 ref2Fw, bit 2 isStranded), indexed like `tasks`
+  int32_t             intron_open = 0, intron_off_edge = 0;
+  const uint32_t*     task_flags = nullptr;
 };
 
 template <int KIND>
@@ -82,6 +86,11 @@ template <>
 struct KindTraits<2> {
   static const int NS = 4, BITS = 2;
   typedef uint8_t cell_t;
+};
+template <>
+struct KindTraits<3> {  // match, delete, insert, jump, intron: the reference's own 5 x 3-bit uint16_t cell (GlobalJumpIntronAligner.hpp:113-118)
+  static const int NS = 5, BITS = 3;
+  typedef uint16_t cell_t;
 };
 
 WV_DEV int imax(const int a, const int b) { return (a > b) ? a : b; }
@@ -137,12 +146,16 @@ struct Aligner {
   static const int                  NS = KT::NS;
   static const int                  BITS = KT::BITS;
   static const int                  FMASK = (1 << KT::BITS) - 1;  // a stored field is (7 - state) & FMASK
+  static const bool                 TWOREF = (KIND == 2 || KIND == 3);  // two references and the jump state
+  static const bool                 INTRON = (KIND == 3);
+  static const unsigned             RC_ACCEPTOR = 0x100u, RC_DONOR = 0x200u;  // KIND 3: flags of a row, beside its base byte
 
   const AlignParams& P;
   const uint8_t*     query;
   const uint8_t*     ref1;
   const uint8_t*     ref2;
   unsigned           Q, R1, R2, G;
+  unsigned           flags = 0;              // KIND 3: AlignParams::task_flags of this task
   cell_t*            ptr;
   static const bool     MULTI = (E == 32);   // the widest kernel also takes longer queries, in strips
   static const unsigned STRIPW = 64u * E;    // query columns per strip
@@ -157,18 +170,55 @@ struct Aligner {
     return (g0 < R1) ? ref1[g0] : ref2[g0 - R1];
   }
 
+  /// What the sweep feeds along the lanes for combined row g0 (0-based, < G): the base byte and, for KIND 3, the row's two splice
+  /// predicates (GlobalJumpIntronAlignerImpl.hpp:33-51).  Both look at raw bytes of the row's OWN reference only: no acceptor in a
+  /// reference's first two rows, no donor in its last one; an unstranded task accepts the motifs of both strands.
+  WV_DEV unsigned refSym(const unsigned g0) const
+  {
+    unsigned c = refChar(g0);
+    if (INTRON) {
+      const bool     in2 = (g0 >= R1);
+      const uint8_t* rf  = in2 ? ref2 : ref1;
+      const unsigned i = in2 ? g0 - R1 : g0, len = in2 ? R2 : R1;
+      const bool     fw = ((flags >> (in2 ? 1 : 0)) & 1u) != 0, stranded = (flags & 4u) != 0;
+      const bool     useFw = fw || !stranded, useRv = !fw || !stranded;
+      if (i >= 2) {  // the intron's last two bases: rows i-2, i-1
+        const uint8_t a = rf[i - 2], b = rf[i - 1];
+        if (a == 'A' && ((useFw && b == 'G') || (useRv && b == 'C'))) c |= RC_ACCEPTOR;
+      }
+      if (i + 1 < len) {  // the intron's first two bases: rows i, i+1
+        const uint8_t a = rf[i], b = rf[i + 1];
+        if (b == 'T' && ((useFw && a == 'G') || (useRv && a == 'C'))) c |= RC_DONOR;
+      }
+    }
+    return c;
+  }
+
   /// back-pointer for `state` stored at cell (q,g); boundary rows/columns are constants
   /// (GlobalAlignerImpl.hpp:66-80,98-107; GlobalJumpAlignerImpl.hpp:77-94,108-118)
   WV_DEV int ptrField(const unsigned q, const unsigned g, const int state) const
   {
     if (q == 0 || g == 0) {
-      if (KIND != 2 && g == 0 && state == ST_INSERT && P.allow_edge_ins) return ST_INSERT;
+      if (!TWOREF && g == 0 && state == ST_INSERT && P.allow_edge_ins) return ST_INSERT;
       return ST_MATCH;
     }
     const unsigned strip = MULTI ? (q - 1) / STRIPW : 0u, qs = MULTI ? (q - 1) % STRIPW : (q - 1);
     const unsigned l = qs / E, e = qs % E;
     const uint64_t idx = uint64_t(strip) * stripCells + (uint64_t(g + l) * E + e) * 64 + l;
     return (7 - ((int(ptr[PAIR ? 2 * idx : idx]) >> (state * BITS)) & FMASK)) & FMASK;
+  }
+
+  /// KIND 3, one column of a reference's last row in the off-edge scan (GlobalJumpIntronAlignerImpl.hpp:237-246, :372-381): the better of
+  /// falling off in the match state (`v` on entry) and in the intron state, ties to match.  `qk` becomes 2 q + (1 for the intron state):
+  /// the scan's "first best wins" order over q is kept and the state rides along in the wave reduction.
+  WV_DEV void offEdgeIntron(int& v, unsigned& qk, const int intron, const unsigned q, const int iOffEdge) const
+  {
+    const int vI = intron + int((Q - q) * unsigned(iOffEdge));
+    qk           = 2 * q;
+    if (!(v >= vI)) {
+      v  = vI;
+      qk = 2 * q + 1;
+    }
   }
 
   // ------------------------------------------------------------------------------------------------
@@ -178,12 +228,13 @@ struct Aligner {
   {
     const int      lane = wv::lane();
     const int      open = P.open, extend = P.extend, L = P.extra, offEdge = P.off_edge;
+    const int      iOpen = P.intron_open, iOffEdge = P.intron_off_edge;  // KIND 3
 
     StartCand candRows1 = {0, 0, 0, ST_MATCH, false};  // rows of ref1 (or the single reference) at q=Q
     StartCand candRows2 = {0, 0, 0, ST_MATCH, false};  // rows of ref2 at q=Q
     bool      haveOff1 = false, haveOff2 = false;      // off-edge candidates of this lane's columns
     int       off1Val = 0, off2Val = 0;
-    unsigned  off1Q = 0, off2Q = 0;
+    unsigned  off1Q = 0, off2Q = 0;  // KIND 3: 2 q + (1 if the candidate starts in the intron state)
     int       lastRowIns = ALIGN_BAD;
     unsigned  lQ = 0;
 
@@ -207,20 +258,22 @@ struct Aligner {
       const unsigned q = q0 + 1;
       for (int s = 0; s < NS; ++s) st[s][e] = ALIGN_BAD;
       st[ST_MATCH][e] = int(q * unsigned(offEdge));
-      if (KIND != 2 && P.allow_edge_ins) st[ST_INSERT][e] = open + int(q * unsigned(extend));
+      if (!TWOREF && P.allow_edge_ins) st[ST_INSERT][e] = open + int(q * unsigned(extend));
+      if (INTRON) st[ST_SPLICE][e] = int(q * unsigned(iOffEdge)) + iOpen;  // a live value in row 0 (GlobalJumpIntronAlignerImpl.hpp:110)
     }
     // the strip's left boundary column, row 0, for lane 0 (column 0 in the first strip); other lanes get theirs through
     // the first shifts
     for (int s = 0; s < NS; ++s) lcur[s] = lprev[s] = ALIGN_BAD;
     lcur[ST_MATCH] = lprev[ST_MATCH] = int(qBase * unsigned(offEdge));
-    if (KIND != 2 && P.allow_edge_ins) lcur[ST_INSERT] = lprev[ST_INSERT] = open + int(qBase * unsigned(extend));
+    if (!TWOREF && P.allow_edge_ins) lcur[ST_INSERT] = lprev[ST_INSERT] = open + int(qBase * unsigned(extend));
+    if (INTRON) lcur[ST_SPLICE] = lprev[ST_SPLICE] = int(qBase * unsigned(iOffEdge)) + iOpen;
 
     unsigned curBlk = 0, nextBlk = 0;
     int      curB[NS], nextB[NS];  // boundary rows of the next 64 steps, one row per lane (strips > 0)
     for (int s = 0; s < NS; ++s) curB[s] = nextB[s] = ALIGN_BAD;
     {
       const unsigned i0 = unsigned(lane);
-      nextBlk           = (i0 < G) ? refChar(i0) : 0u;
+      nextBlk           = (i0 < G) ? refSym(i0) : 0u;
       if (MULTI && strip > 0 && i0 < G)
         for (int s = 0; s < NS; ++s) nextB[s] = bndIn[size_t(i0 + 1) * NS + s];
     }
@@ -231,7 +284,7 @@ struct Aligner {
       if (((t - 1) & 63) == 0) {
         curBlk            = nextBlk;
         const unsigned i0 = t - 1 + 64 + unsigned(lane);
-        nextBlk           = (i0 < G) ? refChar(i0) : 0u;
+        nextBlk           = (i0 < G) ? refSym(i0) : 0u;
         if (MULTI && strip > 0) {
           for (int s = 0; s < NS; ++s) {
             curB[s]  = nextB[s];
@@ -267,29 +320,33 @@ struct Aligner {
       const bool active = (g >= 1) && (unsigned(g) <= G);
       if (!active) continue;
 
-      const bool inRef2 = (KIND == 2) && (unsigned(g) > R1);
-      if (KIND == 2 && unsigned(g) == R1 + 1) {
-        // seam (GlobalJumpAlignerImpl.hpp:181-204): off-edge candidates of the last ref1 row, then re-seed
-        // match/del/ins of the live row while PRESERVING jump.
+      const bool inRef2 = TWOREF && (unsigned(g) > R1);
+      if (TWOREF && unsigned(g) == R1 + 1) {
+        // seam (GlobalJumpAlignerImpl.hpp:181-204, GlobalJumpIntronAlignerImpl.hpp:234-258): off-edge candidates of the last ref1
+        // row, then re-seed match/del/ins (and intron) of the live row while PRESERVING jump.
         for (int e = 0; e < E; ++e) {
           const unsigned q = qBase + unsigned(lane) * E + e + 1;
           if (q < Q) {
-            const int v = st[ST_MATCH][e] + int((Q - q) * unsigned(offEdge));
+            int      v  = st[ST_MATCH][e] + int((Q - q) * unsigned(offEdge));
+            unsigned qk = q;
+            if (INTRON) offEdgeIntron(v, qk, st[ST_SPLICE][e], q, iOffEdge);
             if (!haveOff1 || v > off1Val) {
               haveOff1 = true;
               off1Val  = v;
-              off1Q    = q;
+              off1Q    = qk;
             }
           }
           st[ST_MATCH][e]  = int(q * unsigned(offEdge));
           st[ST_DELETE][e] = ALIGN_BAD;
           st[ST_INSERT][e] = ALIGN_BAD;
+          if (INTRON) st[ST_SPLICE][e] = int(q * unsigned(iOffEdge)) + iOpen;
         }
         // the diagonal neighbour (row R1 of the column to the left) is re-seeded the same way; its jump value stays
         // (column 0 has none)
         lprev[ST_MATCH]  = int((qBase + unsigned(lane) * E) * unsigned(offEdge));
         lprev[ST_DELETE] = ALIGN_BAD;
         lprev[ST_INSERT] = ALIGN_BAD;
+        if (INTRON) lprev[ST_SPLICE] = int((qBase + unsigned(lane) * E) * unsigned(iOffEdge)) + iOpen;  // (column 0 too: :253)
         if (lane == 0 && strip == 0) lprev[ST_JUMP] = ALIGN_BAD;
       }
 
@@ -303,7 +360,7 @@ struct Aligner {
         int up[NS];
         for (int s = 0; s < NS; ++s) up[s] = st[s][e];
         const bool firstCol = (e == 0) && (lane == 0) && (strip == 0);
-        const int  sub      = (unsigned(qc[e]) == rc) ? P.match : P.mismatch;
+        const int  sub      = (unsigned(qc[e]) == (INTRON ? (rc & 0xffu) : rc)) ? P.match : P.mismatch;
         int        nv[NS];
         unsigned   code = 0;
         // Arg-max with "lowest state index wins ties" (the reference's strict-'>' scan) in ONE integer max per
@@ -316,13 +373,16 @@ struct Aligner {
         {
           int m = imax(imax(MANTA_PK(diag[ST_MATCH], 0), MANTA_PK(diag[ST_DELETE], 1)), MANTA_PK(diag[ST_INSERT], 2));
           if (KIND == 1) m = imax(imax(m, MANTA_PK(diag[ST_JUMP], 3)), MANTA_PK(diag[ST_JUMPINS], 4));
-          if (KIND == 2 && inRef2) m = imax(m, MANTA_PK(diag[ST_JUMP], 3));
+          if (TWOREF && inRef2) m = imax(m, MANTA_PK(diag[ST_JUMP], 3));
+          // out of the intron only behind an acceptor motif, and only if strictly better (the lowest tie-break code of all)
+          if (INTRON && (rc & RC_ACCEPTOR)) m = imax(m, MANTA_PK(diag[ST_SPLICE], ST_SPLICE));
           nv[ST_MATCH] = (m >> 3) + sub;
           code |= unsigned(m & FMASK) << (ST_MATCH * BITS);
         }
         // delete
         {
-          int m = imax(imax(MANTA_PKA(up[ST_MATCH], open, 0), MANTA_PK(up[ST_DELETE], 1)), MANTA_PK(up[ST_INSERT], 2));
+          // (the intron aligner alone charges the open score on insert -> delete, GlobalJumpIntronAlignerImpl.hpp:167)
+          int m = imax(imax(MANTA_PKA(up[ST_MATCH], open, 0), MANTA_PK(up[ST_DELETE], 1)), MANTA_PKA(up[ST_INSERT], INTRON ? open : 0, 2));
           if (KIND == 1) m = imax(imax(m, MANTA_PK(ALIGN_BAD, 3)), MANTA_PK(up[ST_JUMPINS], 4));
           int b = (m >> 3) + extend;
           if (firstCol && !inRef2) b = ALIGN_BAD;  // no reset in ref2 (GlobalJumpAlignerImpl.hpp:240-246)
@@ -332,7 +392,7 @@ struct Aligner {
         // insert
         {
           int m = imax(imax(MANTA_PKA(left[ST_MATCH], open, 0), MANTA_PK(ALIGN_BAD, 1)), MANTA_PK(left[ST_INSERT], 2));
-          if (KIND == 2 && inRef2) m = imax(m, MANTA_PK(left[ST_JUMP], 3));  // jump->ins pays no open (:251-256)
+          if (TWOREF && inRef2) m = imax(m, MANTA_PK(left[ST_JUMP], 3));  // jump->ins pays no open (:251-256)
           int b = (m >> 3) + extend;
           if (firstCol && !inRef2) b = ALIGN_BAD;
           nv[ST_INSERT] = b;
@@ -355,7 +415,13 @@ struct Aligner {
             code |= unsigned(m & FMASK) << (ST_JUMPINS * BITS);
           }
         }
-        if (KIND == 2) {
+        if (INTRON) {  // GlobalJumpIntronAlignerImpl.hpp:186-197, :326-337: stay unless a donor motif starts here and match + open is better
+          const int  fromM = up[ST_MATCH] + iOpen;
+          const bool enter = (rc & RC_DONOR) && (fromM > up[ST_SPLICE]);
+          nv[ST_SPLICE]    = enter ? fromM : up[ST_SPLICE];
+          code |= unsigned((7 - (enter ? ST_MATCH : ST_SPLICE)) & FMASK) << (ST_SPLICE * BITS);
+        }
+        if (TWOREF) {
           if (!inRef2) {  // uses THIS cell's final match / ins (GlobalJumpAlignerImpl.hpp:153-161)
             int m = imax(imax(MANTA_PKA(nv[ST_MATCH], L, 0), MANTA_PK(ALIGN_BAD, 1)), MANTA_PKA(nv[ST_INSERT], L, 2));
             m     = imax(m, MANTA_PK(up[ST_JUMP], 3));
@@ -400,11 +466,13 @@ struct Aligner {
         for (int e = 0; e < E; ++e) {
           const unsigned q = qBase + unsigned(lane) * E + e + 1;
           if (q < Q) {
-            const int v = st[ST_MATCH][e] + int((Q - q) * unsigned(offEdge));
+            int      v  = st[ST_MATCH][e] + int((Q - q) * unsigned(offEdge));
+            unsigned qk = q;
+            if (INTRON) offEdgeIntron(v, qk, st[ST_SPLICE][e], q, iOffEdge);
             if (!haveOff2 || v > off2Val) {
               haveOff2 = true;
               off2Val  = v;
-              off2Q    = q;
+              off2Q    = qk;
             }
           }
         }
@@ -415,22 +483,29 @@ struct Aligner {
 
     // q == 0 off-edge candidates (column 0 holds match == 0 on every row >= 1)
     if (lane == 0) {
-      const int v0 = int(Q * unsigned(offEdge));
-      if (KIND == 2) {
+      int      v0 = int(Q * unsigned(offEdge));
+      unsigned q0 = 0;
+      if (INTRON) offEdgeIntron(v0, q0, ALIGN_BAD, 0, iOffEdge);  // (column 0 holds intron == badVal on those rows)
+      if (TWOREF) {
         if (!haveOff1 || v0 >= off1Val) {  // q=0 precedes every other q in scan order
           haveOff1 = true;
           off1Val  = v0;
-          off1Q    = 0;
+          off1Q    = q0;
         }
       }
       if (!haveOff2 || v0 >= off2Val) {
         haveOff2 = true;
         off2Val  = v0;
-        off2Q    = 0;
+        off2Q    = q0;
       }
     }
     waveArgmaxFirst(haveOff2, off2Val, off2Q);
-    if (KIND == 2) waveArgmaxFirst(haveOff1, off1Val, off1Q);
+    if (TWOREF) waveArgmaxFirst(haveOff1, off1Val, off1Q);
+    const int off1State = (INTRON && (off1Q & 1u)) ? ST_SPLICE : ST_MATCH, off2State = (INTRON && (off2Q & 1u)) ? ST_SPLICE : ST_MATCH;
+    if (INTRON) {
+      off1Q >>= 1;
+      off2Q >>= 1;
+    }
 
     // combine in the reference's evaluation order, first best wins
     StartCand best;
@@ -439,15 +514,15 @@ struct Aligner {
     best.query = Q;
     best.state = ST_MATCH;
     best.init  = true;
-    if (KIND == 2) {
-      candUpdate(best, off1Val, R1, off1Q, ST_MATCH);
+    if (TWOREF) {
+      candUpdate(best, off1Val, R1, off1Q, off1State);
       const int      v2 = wv::readlane(candRows2.val, int(lQ));
       const unsigned r2 = wv::readlane(candRows2.ref, int(lQ));
       candUpdate(best, v2, r2, Q, ST_MATCH);
     } else if (P.allow_edge_ins) {
       candUpdate(best, wv::readlane(lastRowIns, int(lQ)), G, Q, ST_INSERT);
     }
-    candUpdate(best, off2Val, G, off2Q, ST_MATCH);
+    candUpdate(best, off2Val, G, off2Q, off2State);
     return best;
   }
 
@@ -632,8 +707,10 @@ struct Aligner {
       const bool isRef1 = (r <= R1);
       const int  pathId = isRef1 ? 0 : 1;
       if (state != ST_JUMP) {
+        // (KIND 3: the intron state walks up the rows like a delete, 64 rows per round trip, and emits 'N', JumpAlignerBaseImpl.hpp:153-158)
         const bool     isM = (state == ST_MATCH);
-        const bool     isD = (state == ST_DELETE);
+        const bool     isN = INTRON && (state == ST_SPLICE);
+        const bool     isD = (state == ST_DELETE) || isN;
         const unsigned dq  = isD ? 0u : 1u;
         const unsigned dg  = (isM || isD) ? 1u : 0u;
         unsigned       limit = isM ? ((q < r) ? q : r) : (isD ? r : q);
@@ -650,10 +727,10 @@ struct Aligner {
           next               = wv::readlane(field, int(run));
         } else {
           moves = window;
-          // stepped diagonally out of ref2's first row with MATCH->MATCH (:128)
-          if (!isRef1 && isM && moves == (r - R1)) isRef2End = true;
+          // stepped diagonally out of ref2's first row with MATCH->MATCH (:128), or up out of it with SPLICE->SPLICE (:154)
+          if (!isRef1 && (isM || isN) && moves == (r - R1)) isRef2End = true;
         }
-        updatePath(rs, pathId, psType, psLen, isM ? OP_M : (isD ? OP_D : OP_I));
+        updatePath(rs, pathId, psType, psLen, isM ? OP_M : (isN ? OP_N : (isD ? OP_D : OP_I)));
         psLen += moves;
         q -= moves * dq;
         r -= moves * dg;
@@ -705,7 +782,7 @@ struct Aligner {
       if (((raw >> 4) & 1) == 0) {
         have1 = true;
         if (tp == OP_M || tp == OP_I || tp == OP_S) p1Read += len;
-        if (tp == OP_M || tp == OP_D) p1Ref += len;
+        if (tp == OP_M || tp == OP_D || tp == OP_N) p1Ref += len;  // apath_ref_length counts the skip
       } else {
         have2 = true;
       }
@@ -758,7 +835,7 @@ struct Aligner {
     ref2  = T.ref2;
     Q     = T.query_len;
     R1    = T.ref1_len;
-    R2    = (KIND == 2) ? T.ref2_len : 0;
+    R2    = TWOREF ? T.ref2_len : 0;
     G     = R1 + R2;
     ptr   = reinterpret_cast<cell_t*>(ptrSlab);
     nStrips    = MULTI ? (Q + STRIPW - 1) / STRIPW : 1u;
@@ -771,7 +848,7 @@ struct Aligner {
     const StartCand start = sweep();
     wv::sync();  // back-pointers written by all lanes are read by all lanes below
     AlignResultDev r;
-    if (KIND == 2)
+    if (TWOREF)
       tracebackJump(start, T, r);
     else
       tracebackSingle(start, T, r);
@@ -782,7 +859,7 @@ struct Aligner {
 /// bytes of back-pointer slab one alignment needs (host + device agree on this)
 WV_HD uint64_t alignPtrSlabBytes(const int kind, const int E, const uint64_t totalRefLen)
 {
-  const uint64_t cellBytes = (kind == 1) ? 2 : 1;
+  const uint64_t cellBytes = (kind == 1 || kind == 3) ? 2 : 1;
   return (totalRefLen + 64 + 1) * uint64_t(E) * 64 * cellBytes;
 }
 
@@ -794,7 +871,7 @@ WV_HD uint64_t alignSlabRefLen(const int kind, const int E, const uint64_t query
   if (E != 32 || queryLen <= stripW) return totalRefLen;
   const uint64_t nStrips = (queryLen + stripW - 1) / stripW;
   const uint64_t unit    = alignPtrSlabBytes(kind, E, 0) / 65;  // bytes per reference row
-  const uint64_t ns      = (kind == 1) ? 5 : ((kind == 2) ? 4 : 3);
+  const uint64_t ns      = (kind == 1 || kind == 3) ? 5 : ((kind == 2) ? 4 : 3);
   const uint64_t need    = nStrips * alignPtrSlabBytes(kind, E, totalRefLen) + 2 * (totalRefLen + 2) * ns * 4 + 64;
   return (need + unit - 1) / unit;  // (generous by the 65 rows alignPtrSlabBytes adds)
 }
@@ -813,6 +890,7 @@ WV_KERNEL_OCC(E == 8 ? 4 : 1) void align_kernel(const AlignParams P)
     if (slot >= nTasks) break;
     const unsigned      tid = P.task_ids ? P.task_ids[slot] : slot;
     Aligner<KIND, E>    al(P);
+    if (KIND == 3) al.flags = P.task_flags[tid];
     al.run(P.tasks[tid], P.results[tid], slab);
     wv::sync();
   }
@@ -841,6 +919,11 @@ MANTA_ALIGN_INST(extern, 1)
 MANTA_ALIGN_INST(, 2)
 #else
 MANTA_ALIGN_INST(extern, 2)
+#endif
+#if MANTA_TU == MANTA_TU_ALIGN3
+MANTA_ALIGN_INST(, 3)
+#else
+MANTA_ALIGN_INST(extern, 3)
 #endif
 #undef MANTA_ALIGN_INST
 #endif

@@ -50,17 +50,28 @@ const char* manta_ctx_device_name(const manta_ctx_t* ctx)
   return ctx ? ctx->deviceName.c_str() : "";
 }
 
-int manta_align_batch(
-    manta_ctx_t* ctx, int kind, const manta_align_scores_t* scores, int32_t extra_score, uint32_t n_tasks,
-    const manta_align_task_t* tasks, const uint8_t* seq_arena, uint64_t seq_arena_bytes, manta_align_result_t* results,
-    uint32_t* cigar_arena, uint64_t cigar_arena_cap, uint64_t* cigar_arena_used)
+}  // extern "C"
+
+/// manta_align_batch and manta_align_intron_batch: validation, bucketing by columns per lane, staging, one launch per bucket, and the
+/// compaction of the cigars are the same for all four kinds; MANTA_ALIGNER_JUMP_INTRON adds two scores and the per-task strand flags
+static int alignBatch(
+    const char* fn, manta_ctx_t* ctx, int kind, const manta_align_scores_t* scores, int32_t extra_score, int32_t intron_open_score,
+    int32_t intron_off_edge_score, uint32_t n_tasks, const manta_align_task_t* tasks, const uint8_t* seq_arena, uint64_t seq_arena_bytes,
+    manta_align_result_t* results, uint32_t* cigar_arena, uint64_t cigar_arena_cap, uint64_t* cigar_arena_used)
 {
+  const std::string name(fn);
+  const bool        intron = (kind == MANTA_ALIGNER_JUMP_INTRON);
   if (!ctx) return MANTA_E_INVALID_ARG;
   if (!scores || (n_tasks && (!tasks || !seq_arena || !results || !cigar_arena)))
-    return fail(ctx, MANTA_E_INVALID_ARG, "manta_align_batch: null argument");
-  if (kind < 0 || kind > 2) return fail(ctx, MANTA_E_INVALID_ARG, "manta_align_batch: unknown aligner kind");
+    return fail(ctx, MANTA_E_INVALID_ARG, name + ": null argument");
   if (kind == MANTA_ALIGNER_JUMP && scores->is_allow_edge_insertion)
     return fail(ctx, MANTA_E_INVALID_ARG, "GlobalJumpAligner does not support isAllowEdgeInsertion");
+  if (intron && scores->is_allow_edge_insertion)  // GlobalJumpIntronAligner.hpp:42-43
+    return fail(ctx, MANTA_E_INVALID_ARG, "GlobalJumpIntronAligner does not support isAllowEdgeInsertion");
+  if (intron)
+    for (uint32_t i = 0; i < n_tasks; ++i)
+      if (tasks[i].reserved & ~uint32_t(MANTA_INTRON_REF1_FW | MANTA_INTRON_REF2_FW | MANTA_INTRON_STRANDED))
+        return fail(ctx, MANTA_E_INVALID_ARG, name + ": task " + std::to_string(i) + " has unknown flag bits");
   if (cigar_arena_used) *cigar_arena_used = 0;
   if (n_tasks == 0) return MANTA_OK;
 
@@ -77,10 +88,10 @@ int manta_align_batch(
       const manta_align_task_t& t(tasks[i]);
       manta_align_result_t&     r(results[i]);
       std::memset(&r, 0, sizeof(r));
-      const bool jump = (kind == MANTA_ALIGNER_JUMP);
+      const bool jump = (kind == MANTA_ALIGNER_JUMP) || intron;
       auto outside = [&](uint64_t off, uint64_t len) { return off > seq_arena_bytes || len > seq_arena_bytes - off; };
       if (outside(t.query_off, t.query_len) || outside(t.ref1_off, t.ref1_len) || (jump && outside(t.ref2_off, t.ref2_len)))
-        return fail(ctx, MANTA_E_INVALID_ARG, "manta_align_batch: task " + std::to_string(i) + " outside the sequence arena");
+        return fail(ctx, MANTA_E_INVALID_ARG, name + ": task " + std::to_string(i) + " outside the sequence arena");
       if (t.query_len == 0 || t.ref1_len == 0 || (jump && t.ref2_len == 0)) {
         r.status = MANTA_E_EMPTY_SEQ;  // GlobalJumpAlignerImpl.hpp:50-58, GlobalAlignerImpl.hpp:44-49
         worst    = MANTA_E_EMPTY_SEQ;
@@ -96,7 +107,7 @@ int manta_align_batch(
       d.ref2_len  = jump ? t.ref2_len : 0;
       d.cigar_off = uint32_t(cigarDevWords);
       cigarDevWords += 4ull * t.query_len + 16;
-      if (cigarDevWords > 0xffffffffull) return fail(ctx, MANTA_E_UNSUPPORTED, "manta_align_batch: batch too large (cigar workspace)");
+      if (cigarDevWords > 0xffffffffull) return fail(ctx, MANTA_E_UNSUPPORTED, name + ": batch too large (cigar workspace)");
       buckets[eIdx].push_back(i);
       bucketMaxRef[eIdx] = std::max<uint64_t>(bucketMaxRef[eIdx], alignSlabRefLen(kind, kESet[eIdx], d.query_len, uint64_t(d.ref1_len) + d.ref2_len));
     }
@@ -115,6 +126,13 @@ int manta_align_batch(
     }
     rt::h2d(dSeq, seq_arena, seq_arena_bytes);
     rt::h2d(dTasks, dev.data(), sizeof(AlignTaskDev) * n_tasks);
+    uint32_t* dFlags = nullptr;
+    if (intron) {
+      std::vector<uint32_t> hFlags(n_tasks);
+      for (uint32_t i = 0; i < n_tasks; ++i) hFlags[i] = tasks[i].reserved;
+      dFlags = ctx->dTaskFlags.as<uint32_t>(n_tasks);
+      rt::h2d(dFlags, hFlags.data(), sizeof(uint32_t) * n_tasks);
+    }
     rt::dzero(dCounter, sizeof(uint32_t) * kNumESet);
     rt::dzero(dResults, sizeof(AlignResultDev) * n_tasks);
 
@@ -148,6 +166,9 @@ int manta_align_batch(
       P.off_edge       = scores->off_edge;
       P.allow_edge_ins = scores->is_allow_edge_insertion ? 1 : 0;
       P.extra          = extra_score;
+      P.intron_open     = intron_open_score;
+      P.intron_off_edge = intron_off_edge_score;
+      P.task_flags      = dFlags;
       rt::Event e0, e1;
       e0.record();
       launchAlignKind(kind, b, grid, P, pair);
@@ -174,7 +195,7 @@ int manta_align_batch(
         continue;
       }
       const uint64_t n = uint64_t(h.cigar1_len) + h.cigar2_len;
-      if (used + n > cigar_arena_cap) return fail(ctx, MANTA_E_CAPACITY, "manta_align_batch: cigar arena too small");
+      if (used + n > cigar_arena_cap) return fail(ctx, MANTA_E_CAPACITY, name + ": cigar arena too small");
       std::memcpy(cigar_arena + used, hcig.data() + dev[i].cigar_off, sizeof(uint32_t) * n);
       r.score            = h.score;
       r.is_jumped        = h.is_jumped;
@@ -189,11 +210,34 @@ int manta_align_batch(
       used += n;
     }
     if (cigar_arena_used) *cigar_arena_used = used;
-    if (worst != MANTA_OK) return fail(ctx, worst, "manta_align_batch: one or more tasks failed; see per-task status");
+    if (worst != MANTA_OK) return fail(ctx, worst, name + ": one or more tasks failed; see per-task status");
     return MANTA_OK;
   } catch (const std::exception& e) {
     return fail(ctx, MANTA_E_HIP, e.what());
   }
+}
+
+extern "C" {
+
+int manta_align_batch(
+    manta_ctx_t* ctx, int kind, const manta_align_scores_t* scores, int32_t extra_score, uint32_t n_tasks,
+    const manta_align_task_t* tasks, const uint8_t* seq_arena, uint64_t seq_arena_bytes, manta_align_result_t* results,
+    uint32_t* cigar_arena, uint64_t cigar_arena_cap, uint64_t* cigar_arena_used)
+{
+  if (!ctx) return MANTA_E_INVALID_ARG;
+  // (MANTA_ALIGNER_JUMP_INTRON needs scores this call cannot carry: manta_align_intron_batch)
+  if (kind < 0 || kind > 2) return fail(ctx, MANTA_E_INVALID_ARG, "manta_align_batch: unknown aligner kind");
+  return alignBatch("manta_align_batch", ctx, kind, scores, extra_score, 0, 0, n_tasks, tasks, seq_arena, seq_arena_bytes, results, cigar_arena,
+                    cigar_arena_cap, cigar_arena_used);
+}
+
+int manta_align_intron_batch(
+    manta_ctx_t* ctx, const manta_align_scores_t* scores, int32_t jump_score, int32_t intron_open_score, int32_t intron_off_edge_score,
+    uint32_t n_tasks, const manta_align_task_t* tasks, const uint8_t* seq_arena, uint64_t seq_arena_bytes, manta_align_result_t* results,
+    uint32_t* cigar_arena, uint64_t cigar_arena_cap, uint64_t* cigar_arena_used)
+{
+  return alignBatch("manta_align_intron_batch", ctx, MANTA_ALIGNER_JUMP_INTRON, scores, jump_score, intron_open_score, intron_off_edge_score,
+                    n_tasks, tasks, seq_arena, seq_arena_bytes, results, cigar_arena, cigar_arena_cap, cigar_arena_used);
 }
 
 

@@ -112,7 +112,7 @@ struct manta_ctx {
   std::string deviceName;
   int         cuCount = 0;
   // align scratch
-  DevBuf dSeq, dTasks, dResults, dCigar, dTaskIds, dCounter, dPtrWs;
+  DevBuf dSeq, dTasks, dResults, dCigar, dTaskIds, dCounter, dPtrWs, dTaskFlags;
   DevBuf dSplitTasks, dSplitResults, dSplitTables;
   DevBuf dRc[16];  // manta_read_piles_batch: inputs, workspace, outputs
   rt::Stream stream;  // the context's own stream (manta_align_batch / manta_assemble_batch run on it)
@@ -240,7 +240,9 @@ inline void launchAlignKind(int kind, int eIdx, int grid, const AlignParams& P, 
       launchAlignPair(eIdx, grid, P);
     else
       launchAlignE<1>(eIdx, grid, P);
-  } else if (pair)
+  } else if (kind == MANTA_ALIGNER_JUMP_INTRON)
+    launchAlignE<3>(eIdx, grid, P);
+  else if (pair)
     launchJumpPair(eIdx, grid, P);
   else
     launchAlignE<2>(eIdx, grid, P);

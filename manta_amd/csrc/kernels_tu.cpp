@@ -3,7 +3,7 @@
 // is only declared; the host sources (api.cpp, MANTA_TU_HOST) launch the kernels through their ordinary external handles.
 #include "wave.hpp"
 #if MANTA_TU == MANTA_TU_ALL || MANTA_TU == MANTA_TU_HOST
-#error "kernels_tu.cpp is compiled once per kernel family: -DMANTA_TU=<MANTA_TU_ASM .. MANTA_TU_GLUE>"
+#error "kernels_tu.cpp is compiled once per kernel family: -DMANTA_TU=<MANTA_TU_ASM .. MANTA_TU_ALIGN3>"
 #endif
 
 #if MANTA_TU == MANTA_TU_ASM
@@ -13,7 +13,7 @@
 #include "assemble_kernels.hpp"
 #elif MANTA_TU == MANTA_TU_GRAPH || MANTA_TU == MANTA_TU_GRAPH_BIG || MANTA_TU == MANTA_TU_CONTIG || MANTA_TU == MANTA_TU_REPEAT
 #include "asm_lds.hpp"
-#elif MANTA_TU == MANTA_TU_ALIGN0 || MANTA_TU == MANTA_TU_ALIGN1 || MANTA_TU == MANTA_TU_ALIGN2
+#elif MANTA_TU == MANTA_TU_ALIGN0 || MANTA_TU == MANTA_TU_ALIGN1 || MANTA_TU == MANTA_TU_ALIGN2 || MANTA_TU == MANTA_TU_ALIGN3
 #include "align_kernels.hpp"
 #elif MANTA_TU == MANTA_TU_ALIGN_PAIR
 #include "align_pair.hpp"

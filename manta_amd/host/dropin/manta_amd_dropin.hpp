@@ -58,13 +58,21 @@ inline void toPath(const uint32_t* cig, const unsigned n, ALIGNPATH::path_t& pat
   for (unsigned i = 0; i < n; ++i) path.push_back(ALIGNPATH::path_segment(map[cig[i] & 15u], cig[i] >> 4));
 }
 
-/// one alignment through manta_align_batch; the reference's own input checks and messages
+/// the intron aligner's extra arguments (manta_align_intron_batch)
+struct IntronArgs {
+  int32_t  openScore, offEdgeScore;
+  uint32_t flags;  ///< MANTA_INTRON_*
+};
+
+/// one alignment through manta_align_batch (manta_align_intron_batch for MANTA_ALIGNER_JUMP_INTRON: `intron` is then required); the
+/// reference's own input checks and messages
 template <typename SymIter>
 manta_align_result_t alignOne(
     const int kind, const manta_align_scores_t& sc, const int32_t extra, SymIter qb, SymIter qe, SymIter r1b, SymIter r1e, SymIter r2b,
-    SymIter r2e, std::vector<uint32_t>& cigar)
+    SymIter r2e, std::vector<uint32_t>& cigar, const IntronArgs* intron)
 {
   using illumina::common::GeneralException;
+  const bool twoRefs = (kind == MANTA_ALIGNER_JUMP || kind == MANTA_ALIGNER_JUMP_INTRON);
   std::vector<uint8_t> arena(qb, qe);
   manta_align_task_t   t{};
   t.query_len = uint32_t(arena.size());
@@ -76,16 +84,32 @@ manta_align_result_t alignOne(
   t.ref2_len = uint32_t(arena.size() - t.ref2_off);
   if (t.query_len == 0) BOOST_THROW_EXCEPTION(GeneralException("Unexpected empty query sequence"));
   if (t.ref1_len == 0)
-    BOOST_THROW_EXCEPTION(GeneralException(kind == MANTA_ALIGNER_JUMP ? "Unexpected empty reference1 sequence" : "Unexpected empty reference sequence"));
-  if (kind == MANTA_ALIGNER_JUMP && t.ref2_len == 0) BOOST_THROW_EXCEPTION(GeneralException("Unexpected empty reference2 sequence"));
+    BOOST_THROW_EXCEPTION(GeneralException(twoRefs ? "Unexpected empty reference1 sequence" : "Unexpected empty reference sequence"));
+  if (twoRefs && t.ref2_len == 0) BOOST_THROW_EXCEPTION(GeneralException("Unexpected empty reference2 sequence"));
   arena.push_back(0);
   cigar.assign(2 * size_t(t.query_len) + 16, 0);
   manta_align_result_t res{};
   uint64_t             used = 0;
   manta_ctx_t*         ctx  = threadContext();
-  const int rc = manta_align_batch(ctx, kind, &sc, extra, 1, &t, arena.data(), arena.size() - 1, &res, cigar.data(), cigar.size(), &used);
+  int                  rc;
+  if (kind == MANTA_ALIGNER_JUMP_INTRON) {
+    t.reserved = intron->flags;
+    rc = manta_align_intron_batch(ctx, &sc, extra, intron->openScore, intron->offEdgeScore, 1, &t, arena.data(), arena.size() - 1, &res, cigar.data(),
+                                  cigar.size(), &used);
+  } else {
+    rc = manta_align_batch(ctx, kind, &sc, extra, 1, &t, arena.data(), arena.size() - 1, &res, cigar.data(), cigar.size(), &used);
+  }
   if (rc != MANTA_OK) BOOST_THROW_EXCEPTION(GeneralException(std::string("manta_amd aligner: ") + manta_last_error(ctx)));
   return res;
+}
+
+/// the three aligners that need no more than manta_align_batch carries
+template <typename SymIter>
+manta_align_result_t alignOne(
+    const int kind, const manta_align_scores_t& sc, const int32_t extra, SymIter qb, SymIter qe, SymIter r1b, SymIter r1e, SymIter r2b,
+    SymIter r2e, std::vector<uint32_t>& cigar)
+{
+  return alignOne(kind, sc, extra, qb, qe, r1b, r1e, r2b, r2e, cigar, static_cast<const IntronArgs*>(nullptr));
 }
 
 }  // namespace manta_amd_dropin

@@ -377,12 +377,19 @@ inline void toPath(const uint32_t* cig, unsigned n, ALIGNPATH::path_t& path)
   for (unsigned i = 0; i < n; ++i) path.emplace_back(ALIGNPATH::fromBamOp(cig[i] & 15u), cig[i] >> 4);
 }
 
-/// one alignment through manta_align_batch
+/// the intron aligner's extra arguments (manta_align_intron_batch)
+struct IntronArgs {
+  int32_t  openScore, offEdgeScore;
+  uint32_t flags;  ///< MANTA_INTRON_*
+};
+
+/// one alignment through manta_align_batch (manta_align_intron_batch for MANTA_ALIGNER_JUMP_INTRON: `intron` is then required)
 template <typename SymIter>
 manta_align_result_t alignOne(
     int kind, const manta_align_scores_t& sc, int32_t extra, SymIter qb, SymIter qe, SymIter r1b, SymIter r1e, SymIter r2b,
-    SymIter r2e, std::vector<uint32_t>& cigar)
+    SymIter r2e, std::vector<uint32_t>& cigar, const IntronArgs* intron = nullptr)
 {
+  const bool twoRefs = (kind == MANTA_ALIGNER_JUMP || kind == MANTA_ALIGNER_JUMP_INTRON);
   std::vector<uint8_t> arena(qb, qe);
   manta_align_task_t   t{};
   t.query_off = 0;
@@ -395,14 +402,21 @@ manta_align_result_t alignOne(
   t.ref2_len = uint32_t(arena.size() - t.ref2_off);
   // the reference's own checks, same messages (GlobalJumpAlignerImpl.hpp:50-58, GlobalAlignerImpl.hpp:44-49)
   if (t.query_len == 0) throw GeneralException("Unexpected empty query sequence");
-  if (t.ref1_len == 0) throw GeneralException(kind == MANTA_ALIGNER_JUMP ? "Unexpected empty reference1 sequence" : "Unexpected empty reference sequence");
-  if (kind == MANTA_ALIGNER_JUMP && t.ref2_len == 0) throw GeneralException("Unexpected empty reference2 sequence");
+  if (t.ref1_len == 0) throw GeneralException(twoRefs ? "Unexpected empty reference1 sequence" : "Unexpected empty reference sequence");
+  if (twoRefs && t.ref2_len == 0) throw GeneralException("Unexpected empty reference2 sequence");
   arena.push_back(0);
   cigar.assign(2 * size_t(t.query_len) + 16, 0);
   manta_align_result_t res{};
   uint64_t             used = 0;
   manta_ctx_t*         ctx  = threadContext();
-  const int rc = manta_align_batch(ctx, kind, &sc, extra, 1, &t, arena.data(), arena.size() - 1, &res, cigar.data(), cigar.size(), &used);
+  int                  rc;
+  if (kind == MANTA_ALIGNER_JUMP_INTRON) {
+    t.reserved = intron->flags;
+    rc = manta_align_intron_batch(ctx, &sc, extra, intron->openScore, intron->offEdgeScore, 1, &t, arena.data(), arena.size() - 1, &res, cigar.data(),
+                                  cigar.size(), &used);
+  } else {
+    rc = manta_align_batch(ctx, kind, &sc, extra, 1, &t, arena.data(), arena.size() - 1, &res, cigar.data(), cigar.size(), &used);
+  }
   if (rc != MANTA_OK) throw GeneralException(std::string("manta_amd aligner: ") + manta_last_error(ctx), rc);
   return res;
 }
@@ -489,6 +503,40 @@ struct GlobalJumpAligner : public AlignerBase<ScoreType> {
 
 private:
   const ScoreType _jumpScore;
+};
+
+/// alignment/GlobalJumpIntronAligner.hpp:32-57 (RNA mode: introns behind GT..AG / CT..AC motifs come back as SKIP segments)
+template <typename ScoreType>
+struct GlobalJumpIntronAligner : public AlignerBase<ScoreType> {
+  GlobalJumpIntronAligner(const AlignmentScores<ScoreType>& scores, const ScoreType jumpScore, const ScoreType intronOpenScore,
+                          const ScoreType intronOffEdgeScore)
+    : AlignerBase<ScoreType>(scores), _jumpScore(jumpScore), _intronOpenScore(intronOpenScore), _intronOffEdgeScore(intronOffEdgeScore)
+  {
+    if (scores.isAllowEdgeInsertion) throw GeneralException("GlobalJumpIntronAligner does not support isAllowEdgeInsertion");
+  }
+  const ScoreType& getJumpScore() const { return _jumpScore; }
+  template <typename SymIter>
+  void align(const SymIter queryBegin, const SymIter queryEnd, const SymIter ref1Begin, const SymIter ref1End, const SymIter ref2Begin,
+             const SymIter ref2End, bool ref1Fw, bool ref2Fw, bool isStranded, JumpAlignmentResult<ScoreType>& result) const
+  {
+    result.clear();
+    std::vector<uint32_t>      cig;
+    const detail::IntronArgs   ia = {int32_t(_intronOpenScore), int32_t(_intronOffEdgeScore),
+                                     uint32_t((ref1Fw ? MANTA_INTRON_REF1_FW : 0) | (ref2Fw ? MANTA_INTRON_REF2_FW : 0) |
+                                              (isStranded ? MANTA_INTRON_STRANDED : 0))};
+    const manta_align_result_t r = detail::alignOne(MANTA_ALIGNER_JUMP_INTRON, detail::toAbi(this->_scores), int32_t(_jumpScore), queryBegin,
+                                                    queryEnd, ref1Begin, ref1End, ref2Begin, ref2End, cig, &ia);
+    result.score           = ScoreType(r.score);
+    result.jumpInsertSize  = r.jump_insert_size;
+    result.jumpRange       = r.jump_range;
+    result.align1.beginPos = r.begin_pos1;
+    result.align2.beginPos = r.begin_pos2;
+    detail::toPath(cig.data() + r.cigar1_off, r.cigar1_len, result.align1.apath);
+    detail::toPath(cig.data() + r.cigar2_off, r.cigar2_len, result.align2.apath);
+  }
+
+private:
+  const ScoreType _jumpScore, _intronOpenScore, _intronOffEdgeScore;
 };
 
 }  // namespace manta_amd

@@ -9,7 +9,7 @@
 // 1422-1849, 1860-2303; manta/SVReferenceUtil.cpp:56-205), restated over sv_types.hpp.  The two I/O seams of the
 // reference -- faidx reference fetch and the BAM read scan -- are the RefinerInputSource callbacks.
 // Pinned against the UNMODIFIED reference refiner run in memory (oracle/ref_refiner_driver.cpp) by
-// tests/test_refiner.py.  DNA only: GSCOptions::isRNA is refused (the intron-aware aligner is not on this path).
+// tests/test_refiner.py.  DNA only: GSCOptions::isRNA is refused (the intron-aware aligner exists, manta_align_intron_batch; the refiner's RNA glue around it does not).
 #pragma once
 
 #include <atomic>
@@ -583,6 +583,7 @@ struct SVCandidateAssemblyRefiner {
   SVCandidateAssemblyRefiner(const GSCOptions& opt, const bam_header_info& header, RefinerInputSource& source)
     : _opt(opt), _header(header), _source(source)
   {
+    // (the aligner of that path is on the device -- manta_align_intron_batch --, the RNA branch of this glue is not)
     if (opt.isRNA) throw GeneralException("manta_amd::SVCandidateAssemblyRefiner: the RNA (intron-aware) spanning path is not supported");
   }
 

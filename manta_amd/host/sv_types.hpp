@@ -230,7 +230,7 @@ struct GSCOptions {
   SVRefinerOptions   refineOpt;
   std::string        referenceFilename;
   bool               enableRemoteReadRetrieval = false;
-  bool               isRNA                     = false;  ///< the RNA (intron-aware) spanning path is not on the GPU path: refused
+  bool               isRNA                     = false;  ///< refused: the intron-aware aligner is on the device (manta_align_intron_batch), the refiner's RNA branch is not
   bool               isOutputContig            = false;
 };
 

@@ -430,12 +430,8 @@ int manta_smallsv_upload(
     const bool streamed = b->streamUploads && !std::getenv("MANTA_AMD_NO_STREAM_UPLOAD");
     // a streamed upload starts the DMA of the read bases before anything else: plan()'s pass over the read offsets runs beside it
     const bool noEarlyStream = std::getenv("MANTA_AMD_NO_EARLY_STREAM") != nullptr;  // A/B knob (read per call: the tests flip it)
-    const bool        chunksInFlight = streamed && !noEarlyStream && b->asmStage.startStream(n_loci, bases, read_off, locus_read_begin, b->copy);
-    struct DrainOnFailure {  // (a failed call must not leave DMA reads of the caller's buffers queued)
-      manta_smallsv_t* b;
-      bool             armed;
-      ~DrainOnFailure() { if (armed) drainCopyStream(b); }
-    } drain{b, chunksInFlight};
+    // (the ticket: chunks in flight.  Every return before uploadStreamed() takes it drops it, which drains the copy stream)
+    std::optional<ChunkStream::Ticket> early = (streamed && !noEarlyStream) ? b->asmStage.startStream(n_loci, bases, read_off, locus_read_begin, b->copy) : std::nullopt;
     int rc      = b->asmStage.plan(b->opt, n_loci, read_off, locus_read_begin);
     if (rc != MANTA_OK) return rc;
     const double tP1 = nowMs();
@@ -456,7 +452,7 @@ int manta_smallsv_upload(
     if (streamed) {
       // the assembler does not read the reference windows: they travel on the copy stream BEHIND the read bases and the
       // schedule kernel waits for them (smallsvRunImpl); nothing but the small per-read arrays is waited for here
-      b->asmStage.uploadStreamed(bases, read_off, locus_read_begin, b->copy);  // syncs the small copies, returns with the bases in flight
+      b->asmStage.uploadStreamed(bases, read_off, locus_read_begin, b->copy, std::move(early));  // syncs the small copies, returns with the bases in flight
       rt::ScopedStream onCopy(b->copy);
       rt::h2d(dRefs, refs, b->refBytes);
       rt::h2d(dRefOff, ref_off, sizeof(uint64_t) * (n_loci + 1));
@@ -470,11 +466,11 @@ int manta_smallsv_upload(
       rt::sync();
     }
     if (std::getenv("MANTA_AMD_DEBUG_TIMING"))
-      std::fprintf(stderr, "manta_amd: smallsv_upload plan %.2f ms, upload (%s) %.2f ms\n", tP1 - tP0, b->asmStage.streaming ? "streamed" : "blocking", nowMs() - tP1);
-    drain.armed = false;
+      std::fprintf(stderr, "manta_amd: smallsv_upload plan %.2f ms, upload (%s) %.2f ms\n", tP1 - tP0, b->asmStage.chunks.active() ? "streamed" : "blocking", nowMs() - tP1);
     b->uploaded = true;
     return MANTA_OK;
   } catch (const std::exception& e) {
+    drainCopyStream(b);  // (chunks uploadStreamed() had taken over, with the reference copies behind them)
     return fail(ctx, MANTA_E_HIP, e.what());
   }
 }
@@ -573,7 +569,7 @@ int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates)
       // a second persistent assembler would take exactly those slots and both would spin until the kernels' time-out.
       // Per device, process-wide: never two streamed assemblers on a device at once.
       std::unique_lock<std::mutex> streamedOnly(streamedAsmMu(ctx), std::defer_lock);
-      if (as.streaming) streamedOnly.lock();
+      if (as.chunks.active()) streamedOnly.lock();
       as.stageQueued = false;  // (a run that failed behind its queued staging must not leave the flag to the next one)
       as.earlyStaged = false;
       b->evStart.record();
@@ -850,7 +846,7 @@ int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates)
           b->stats.n_alignments += b->lastSmall[k];
         }
     alignOnly.release();
-    if (as.streaming) {  // all chunks were consumed by the kernel, so this returns at once; it closes the stream's error state
+    if (as.chunks.active()) {  // all chunks were consumed by the kernel, so this returns at once; it closes the stream's error state
       rt::ScopedStream onCopy(b->copy);
       rt::sync();
     }
@@ -1225,7 +1221,7 @@ int spanningRunImpl(manta_spanning_t* b, StageGates* gates)
     {
       GateLock only(gates, &StageGates::asmMu);
       std::unique_lock<std::mutex> streamedOnly(streamedAsmMu(ctx), std::defer_lock);  // see smallsvRunImpl
-      if (as.streaming) streamedOnly.lock();
+      if (as.chunks.active()) streamedOnly.lock();
       as.stageQueued = false;  // (a run that failed behind its queued staging must not leave the flag to the next one)
       as.earlyStaged = false;
       b->evStart.record();
@@ -1320,7 +1316,7 @@ int spanningRunImpl(manta_spanning_t* b, StageGates* gates)
     }
     rt::sync();
     alignOnly.release();
-    if (as.streaming) {  // every chunk was consumed by the kernel, so this returns at once; it closes the copy stream's error state
+    if (as.chunks.active()) {  // every chunk was consumed by the kernel, so this returns at once; it closes the copy stream's error state
       rt::ScopedStream onCopy(b->copy);
       rt::sync();
     }

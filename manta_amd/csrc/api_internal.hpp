@@ -8,7 +8,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <unistd.h>
 #include <functional>
 #include <condition_variable>
 #include <chrono>
@@ -17,6 +16,7 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -31,6 +31,7 @@
 #include "read_class_kernels.hpp"
 #include <unordered_map>
 #include "rt.hpp"
+#include "host_pool.hpp"
 
 using namespace manta_dev;
 
@@ -101,6 +102,7 @@ inline double nowMs()
 inline std::atomic<int> g_liveWorkspaces{0};
 
 }  // namespace manta_host
+#include "upload_stream.hpp"  // (ChunkStream: needs DevBuf / PinnedBuf)
 using namespace manta_host;
 
 struct manta_smallsv;
@@ -327,8 +329,6 @@ inline size_t workspaceBudget(const size_t capBytes)
   return std::min<size_t>(freeNow / 2 / size_t(live), capBytes);
 }
 
-/// Host loops over a whole batch (validation scan of the offset arrays, compaction of the results) split over a few
-/// threads: fn(part, begin, end) for `parts` contiguous ranges of [0, n); the caller's thread takes part 0.
 /// plan()'s inner loops over one locus' reads: dwords of 2-bit codes (16 bases each) and the longest read (all ones: a negative step /
 /// a read of 4 G bases).  The second form is the first compiled for AVX2 -- the host translation units are built for baseline x86-64,
 /// where the loop stays scalar (~1.1 ns per read; the metric's batch has 800 k) -- and is taken where the CPU has it.
@@ -357,108 +357,6 @@ inline void scanOffsetsAvx2(const uint64_t* o, const uint32_t n, uint64_t& wOut,
 inline bool hostHasAvx2() { return false; }
 #endif
 #undef MANTA_SCAN_OFFSETS_BODY
-
-static const unsigned kHostPartsMax = 8;
-inline unsigned hostParts(const uint64_t n)
-{
-  static const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  if (const char* forced = std::getenv("MANTA_AMD_HOST_PARTS"))  // tests: take the multi-range paths on small batches too
-    return unsigned(std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(n, kHostPartsMax), uint64_t(std::max(1, std::atoi(forced))))));
-  if (n < 4096) return 1;
-  return std::min(n < 262144 ? 4u : kHostPartsMax, hw);  // (eight for the passes over every read of a large batch)
-}
-/// seven helper threads per process, parked on a condition variable between jobs (starting std::threads per call costs more
-/// than the loops they would share on a 256-core host)
-class HostPool {
- public:
-  static HostPool& get()
-  {
-    static HostPool pool;
-    return pool;
-  }
-  /// fn(part, begin, end) for `parts` (<= kHostPartsMax) contiguous ranges of [0, n); part 0 runs on the caller's thread.  One job at a
-  /// time: concurrent callers (workers of a batch call) queue up behind runMu.
-  template <typename F>
-  void run(const uint64_t n, const unsigned parts, F fn)
-  {
-    auto begin = [&](unsigned t) { return n * t / parts; };
-    if (parts <= 1 || getpid() != owner) {  // (a fork()ed child has no helper threads: it runs the loop itself)
-      fn(0u, uint64_t(0), n);
-      return;
-    }
-    std::lock_guard<std::mutex> only(runMu);
-    std::function<void(unsigned)> job = [&](unsigned t) { fn(t, begin(t), begin(t + 1)); };
-    {
-      std::lock_guard<std::mutex> g(mu);
-      current = &job;
-      wanted  = parts - 1;
-      pending = parts - 1;
-      ++generation;
-    }
-    cv.notify_all();
-    struct WaitForHelpers {  // also when fn throws on the caller's part: the helpers still hold a pointer to `job`
-      HostPool& p;
-      ~WaitForHelpers()
-      {
-        std::unique_lock<std::mutex> g(p.mu);
-        p.done.wait(g, [&] { return p.pending == 0; });
-        p.current = nullptr;
-      }
-    } waitForHelpers{*this};
-    fn(0u, begin(0), begin(1));
-  }
-
- private:
-  HostPool() : owner(getpid())
-  {
-    for (unsigned i = 0; i + 1 < kHostPartsMax; ++i) threads.emplace_back([this, i] { loop(i + 1); });
-  }
-  ~HostPool()
-  {
-    if (getpid() != owner) {  // fork()ed child: the threads do not exist here
-      for (std::thread& t : threads) t.detach();
-      return;
-    }
-    {
-      std::lock_guard<std::mutex> g(mu);
-      stop = true;
-    }
-    cv.notify_all();
-    for (std::thread& t : threads) t.join();
-  }
-  void loop(const unsigned id)
-  {
-    uint64_t seen = 0;
-    while (true) {
-      std::function<void(unsigned)>* job = nullptr;
-      {
-        std::unique_lock<std::mutex> g(mu);
-        cv.wait(g, [&] { return stop || generation != seen; });
-        if (stop) return;
-        seen = generation;
-        if (id <= wanted) job = current;
-      }
-      if (job) {
-        (*job)(id);
-        std::lock_guard<std::mutex> g(mu);
-        if (--pending == 0) done.notify_one();
-      }
-    }
-  }
-  const pid_t                    owner;
-  std::mutex                     mu, runMu;
-  std::condition_variable        cv, done;
-  std::vector<std::thread>       threads;
-  std::function<void(unsigned)>* current = nullptr;
-  unsigned                       wanted = 0, pending = 0;
-  uint64_t                       generation = 0;
-  bool                           stop = false;
-};
-template <typename F>
-void hostParallel(const uint64_t n, const unsigned parts, F fn)
-{
-  HostPool::get().run(n, parts, fn);
-}
 
 inline uint32_t nextPow2(uint64_t v)
 {
@@ -492,7 +390,6 @@ struct AsmStage {
   {
     g_liveWorkspaces--;
     g_livePerDevice[std::min(kMaxDevices - 1, std::max(0, ctx->deviceId))]--;
-    if (dChunksDone) rt::dfree(dChunksDone);
   }
   AsmStage(const AsmStage&) = delete;
   AsmStage& operator=(const AsmStage&) = delete;
@@ -768,7 +665,6 @@ struct AsmStage {
       // The small class (class 0) runs on contig_pool_kernel (asm_contig.hpp: the workgroup's LDS is a pool the waves take their loci's
       // bytes from) whenever one of its loci fits an empty pool; MANTA_AMD_NO_CONTIG_POOL (A/B runs) keeps it on contig_kernel.
       contigPool = classBytes[0] && classBytes[0] <= CK_POOL_BYTES - CK_POOL_HDR && !std::getenv("MANTA_AMD_NO_CONTIG_POOL");
-      int maxGrid = 1;
       for (unsigned c = 0; c < LG_CLASSES; ++c) {
         gridContig[c] = 0;
         if (!classBytes[c]) continue;
@@ -777,13 +673,11 @@ struct AsmStage {
           const uint64_t wgs   = std::min<uint64_t>({(fastIds.size() + CK_POOL_WAVES - 1) / CK_POOL_WAVES, uint64_t(ctx->cuCount) * perCu,
                                                      wsBudget / (uint64_t(CK_POOL_WAVES) * ckWorkspaceLayout().total)});
           gridContig[c]        = int(CK_POOL_WAVES * std::max<uint64_t>(1, wgs));
-          maxGrid              = std::max(maxGrid, gridContig[c]);
           continue;
         }
         static const int wgCap = std::getenv("MANTA_AMD_CONTIG_WG_CAP") ? std::atoi(std::getenv("MANTA_AMD_CONTIG_WG_CAP")) : 8;  // experiments
         const int perCu = std::max(1, std::min(wgCap, rt::blocksPerCu(contig_kernel, 64, classBytes[c], int(163840 / classBytes[c]))));
         gridContig[c]   = int(std::max<uint64_t>(1, std::min<uint64_t>({fastIds.size(), uint64_t(ctx->cuCount) * perCu, wsBudget / ckWorkspaceLayout().total})));
-        maxGrid         = std::max(maxGrid, gridContig[c]);
       }
       if (std::getenv("MANTA_AMD_DEBUG"))
         for (unsigned c = 0; c < LG_CLASSES; ++c) {
@@ -831,7 +725,6 @@ struct AsmStage {
       if (std::getenv("MANTA_AMD_DEBUG"))
         std::fprintf(stderr, "manta_amd: slab arena of the LDS pipeline: %.1f MB for %zu + %zu loci (cap %.1f MB)\n", double(lgArenaCap) / 1e6, fastIds.size(), bigIds.size(),
                      double(wsBudget / 2) / 1e6);
-      (void)maxGrid;
     }
     // contig + pseudo-read text one locus can emit at worst; the arena holds the typical case for every locus plus one
     // worst case, so a single-locus call (the runIterativeAssembler adapter) can never exhaust it
@@ -874,139 +767,49 @@ struct AsmStage {
   std::vector<uint64_t> plRebased;
   uint64_t              plBytes = 0;
 
-  // ---- streamed upload (whole-batch calls): the read bases arrive chunk by chunk on `copyStream` while assemble_kernel,
-  // launched right away on the pipeline's stream, works through the loci whose chunk has landed (AsmParams::upload_*)
-  static const uint32_t kStreamChunks = 32;  ///< at most (array sizes)
-  /// chunks a streamed upload is cut into: the kernel cannot start on a chunk before all of it has landed, so the last chunk's loci are the
-  /// tail behind the DMA (1 / chunks of the kernel's work); every chunk costs a copy command and a counter write
-  /// Workgroup slots a streamed launch of the LDS pipeline leaves free for the runtime's copy kernels and stream writes (launch()): two
-  /// per XCD.  Workgroups are dealt to the eight XCDs round-robin and stay there, so what matters is a free slot in EVERY XCD: with 4 free
-  /// slots (one in each of four XCDs) a 16 384-locus config-5 block starved until the kernel's time-out, with 16 it runs -- and the quarter
-  /// of the CUs that rounds 4-5 left free cost graph_kernel 12 % and graph_big_kernel 25 % of their workgroups for the whole launch
-  /// (metric step 8.83 -> 8.60 ms, 16 384 config-5 loci 268 -> 257 ms).  MANTA_AMD_STREAM_FREE_WGS overrides (rounded up to whole eights).
-  static int streamFreeSlots(const int cuCount)
-  {
-    static const int forced = std::getenv("MANTA_AMD_STREAM_FREE_WGS") ? std::max(1, std::atoi(std::getenv("MANTA_AMD_STREAM_FREE_WGS"))) : 0;
-    const int        want   = forced ? forced : 16;
-    return std::max(1, std::min(((want + 7) / 8) * 8, cuCount / 4));  // (never more than the quarter of the CUs of rounds 4-5: small devices, the emulator)
-  }
-  static uint32_t streamChunks()
-  {
-    static const uint32_t n = std::getenv("MANTA_AMD_STREAM_CHUNKS") ? uint32_t(std::max(1, std::min(int(kStreamChunks), std::atoi(std::getenv("MANTA_AMD_STREAM_CHUNKS"))))) : 16u;
-    return n;
-  }
-  DevBuf                bPlShift;  // streamed packed piles: three shifts per chunk
-  uint64_t*             dPlShift = nullptr;
-  bool                  streamingPiles = false;
-  DevBuf                bStream;  // chunk shifts
-  uint32_t*             dStream = nullptr;
-  uint32_t*             dChunksDone = nullptr;  // fine-grained device word the copy engine bumps after every chunk
-  PinnedBuf             pChunkIds;              // the values 0..kStreamChunks it is bumped to (DMA sources)
-  uint32_t              chunkLoci = 0;
-  bool                  streaming = false;
+  // ---- streamed upload (whole-batch calls, upload_stream.hpp): the allocations and the small arrays are upload()'s, the chunks `chunks`'
+  ChunkStream chunks;
 
-  /// like upload(), but only ENQUEUES the copy of the read bases (in kStreamChunks pieces, each followed by its completion
-  /// signal) on copyStream and returns; launch() passes the counters to the kernel.  The caller keeps `bases` alive and
-  /// synchronises copyStream before it touches them again.
-  void uploadStreamed(const uint8_t* bases, const uint64_t* read_off, const uint32_t* locus_read_begin, rt::Stream& copyStream)
+  /// like upload(), but only ENQUEUES the copy of the read bases (in chunks, each followed by its completion signal) on copyStream and
+  /// returns; launch() passes the counters to the kernel.  The caller keeps `bases` alive and synchronises copyStream before it touches
+  /// them again.  `ticket`: startStream() has queued this batch's chunks already.
+  void uploadStreamed(const uint8_t* bases, const uint64_t* read_off, const uint32_t* locus_read_begin, rt::Stream& copyStream,
+                      std::optional<ChunkStream::Ticket> ticket = std::nullopt)
   {
-    const bool chunksQueued = preStreamed && preLoci == nLoci;  // startStream() ran for this batch: the chunks are in flight already
-    if (preStreamed && !chunksQueued) {  // (cannot happen: startStream() and plan() are given the same batch)
-      rt::ScopedStream onCopy(copyStream);
-      rt::sync();
-    }
-    preStreamed = false;
-    StreamLayout L;
-    if (chunksQueued)
-      L = preLayout;
-    else
-      L = streamLayout(nLoci, read_off, locus_read_begin);
-    chunkLoci                 = L.chunkLoci;
-    const uint64_t savedBases = nBases;
-    nBases                    = L.cursor + 64;  // device arena incl. the per-chunk padding
-    upload(nullptr, nullptr, chunksQueued ? nullptr : locus_read_begin);  // allocations + the small arrays (order, word lengths, growth schedule, locus begins)
-    nBases  = savedBases;
+    if (ticket && ticket->nLoci != nLoci) throw rt::Error("internal: the early stream was started for another batch");  // (the ticket drains)
+    const ChunkStream::StreamLayout L = ticket ? ticket->layout : ChunkStream::streamLayout(nLoci, read_off, locus_read_begin);
+    // allocations + the small arrays (order, word lengths, growth schedule, locus begins); the arena incl. the per-chunk padding
+    upload(nullptr, nullptr, ticket ? nullptr : locus_read_begin, L.cursor + 64);
     dPlCodes = nullptr;
-    if (!chunksQueued) rt::h2d(dOff, read_off, sizeof(uint64_t) * (nReadsTotal + 1));
-    dStream = bStream.as<uint32_t>(1 + kStreamChunks);
-    rt::h2d(dStream, L.shift, sizeof(uint32_t) * (1 + kStreamChunks));
-    if (!chunksQueued) resetChunkCounter(copyStream);
-    if (chunksQueued) rt::curStreamWaits(evPreSmall);  // (read offsets and locus table: ahead of the chunks on the copy stream)
+    if (!ticket) rt::h2d(dOff, read_off, sizeof(uint64_t) * (nReadsTotal + 1));
+    chunks.begin(ChunkStream::Mode::Bases, L, L.shift);
+    if (!ticket) chunks.reset(copyStream);
+    if (ticket) rt::curStreamWaits(chunks.evPreSmall);
     rt::sync();  // the counter is zero and the small arrays are in place before the first chunk can land / the kernel starts
-    if (!chunksQueued) queueChunks(L, bases, copyStream);
-    streaming = true;
+    if (!ticket) queueBases(L, bases, copyStream);
+    if (ticket) ticket->consume();
   }
-
-  /// where the chunks of a streamed upload lie on the host and on the device (chunks of whole loci, in locus order)
-  struct StreamLayout {
-    uint32_t chunkLoci = 0, nChunks = 0;
-    uint64_t cursor = 0;  ///< bytes of the device arena the chunks take (per-chunk padding included)
-    uint64_t hostBegin[kStreamChunks + 1] = {0}, devBegin[kStreamChunks + 1] = {0};
-    uint32_t shift[1 + kStreamChunks] = {0};  ///< AsmParams::chunk_shift: device - host offset of chunk c at [1 + c]
-    bool     monotone = true;
-  };
-  static StreamLayout streamLayout(const uint32_t n, const uint64_t* read_off, const uint32_t* locus_read_begin)
+  void queueBases(const ChunkStream::StreamLayout& L, const uint8_t* bases, rt::Stream& copyStream)
   {
-    StreamLayout L;
-    L.chunkLoci = std::max<uint32_t>(1, (n + streamChunks() - 1) / streamChunks());
-    L.nChunks   = (n + L.chunkLoci - 1) / L.chunkLoci;
-    for (uint32_t c = 0; c < L.nChunks; ++c) {
-      const uint32_t l0 = c * L.chunkLoci, l1 = std::min(n, l0 + L.chunkLoci);
-      L.hostBegin[c]    = read_off[locus_read_begin[l0]];
-      const uint64_t end = read_off[locus_read_begin[l1]];
-      if (end < L.hostBegin[c]) L.monotone = false;
-      const uint64_t len = end - L.hostBegin[c];
-      L.devBegin[c]      = L.cursor;
-      // (modulo 2^32: the kernel adds it in 32-bit arithmetic to a 64-bit offset; device offsets only grow by the padding, so the shifts stay small)
-      L.shift[1 + c]     = uint32_t(L.devBegin[c] - L.hostBegin[c]);
-      L.cursor           = (L.cursor + len + 64 + 255) & ~uint64_t(255);
-    }
-    L.hostBegin[L.nChunks] = read_off[locus_read_begin[n]];
-    return L;
-  }
-  void resetChunkCounter(rt::Stream& copyStream)
-  {
-    if (!dChunksDone) dChunksDone = static_cast<uint32_t*>(rt::dmallocFine(64));
-    uint32_t* ids = pChunkIds.as<uint32_t>(kStreamChunks + 1);
-    for (uint32_t c = 0; c <= kStreamChunks; ++c) ids[c] = c;
-    {  // a call that failed half way may have left counter bumps queued on the copy stream: none may land after the reset
-      rt::ScopedStream onCopy(copyStream);
-      rt::sync();
-    }
-    rt::h2d(dChunksDone, ids, sizeof(uint32_t));  // = 0
-  }
-  void queueChunks(const StreamLayout& L, const uint8_t* bases, rt::Stream& copyStream)
-  {
-    // one copy per chunk, each followed by a stream-ordered 32-bit write of the counter (command processor; a 4-byte copy
-    // if the runtime refuses): the counter says c+1 only after chunk c is in HBM.  Nothing here needs a workgroup slot --
-    // the persistent assembler, or another process' kernels, may own every one of them.
-    const uint32_t*   ids = pChunkIds.as<uint32_t>(kStreamChunks + 1);
-    rt::ScopedStream onCopy(copyStream);
-    for (uint32_t c = 0; c < L.nChunks; ++c) {
-      rt::h2d(dBases + L.devBegin[c], bases + L.hostBegin[c], L.hostBegin[c + 1] - L.hostBegin[c]);
-      if (!rt::streamWrite32(dChunksDone, c + 1)) rt::h2d(dChunksDone, ids + c + 1, sizeof(uint32_t));
-    }
+    chunks.queue(L.nChunks, copyStream, [&](uint32_t c) { rt::h2d(dBases + L.devBegin[c], bases + L.hostBegin[c], L.hostBegin[c + 1] - L.hostBegin[c]); });
   }
   /// The first thing a streamed upload does, BEFORE plan(): the read bases start for the device while the host still sizes the batch
   /// (plan()'s pass over every read offset: ~0.5 ms for the metric's 800 k reads, which the kernel used to spend waiting for chunks
-  /// later).  Needs nothing of the plan: chunks are whole loci in locus order.  False (nothing queued): offsets that are not monotone
-  /// at the chunk boundaries -- plan() names the error.  The caller drains copyStream if it fails before uploadStreamed().
-  bool                  preStreamed = false;
-  rt::Event             evPreSmall;
-  uint32_t              preLoci     = 0;
-  StreamLayout          preLayout;
-  bool startStream(const uint32_t n_loci, const uint8_t* bases, const uint64_t* read_off, const uint32_t* locus_read_begin, rt::Stream& copyStream)
+  /// later).  Needs nothing of the plan: chunks are whole loci in locus order.  Empty (nothing queued): offsets that are not monotone
+  /// at the chunk boundaries -- plan() names the error.  The ticket goes to uploadStreamed(); dropped on the way, it drains copyStream.
+  std::optional<ChunkStream::Ticket> startStream(const uint32_t n_loci, const uint8_t* bases, const uint64_t* read_off, const uint32_t* locus_read_begin,
+                                                 rt::Stream& copyStream)
   {
-    preStreamed = false;
     for (uint32_t l = 0; l < n_loci; ++l)
-      if (locus_read_begin[l + 1] < locus_read_begin[l]) return false;
-    preLayout = streamLayout(n_loci, read_off, locus_read_begin);
-    if (!preLayout.monotone) return false;
-    dBases = bBases.as<uint8_t>(preLayout.cursor + 64 + 64);  // (upload() asks for the same sizes again)
+      if (locus_read_begin[l + 1] < locus_read_begin[l]) return std::nullopt;
+    const ChunkStream::StreamLayout L = ChunkStream::streamLayout(n_loci, read_off, locus_read_begin);
+    if (!L.monotone) return std::nullopt;
+    std::optional<ChunkStream::Ticket> ticket(ChunkStream::Ticket{L, n_loci, {&copyStream, &ChunkStream::drain}});  // (before anything is queued on copyStream)
+    dBases = bBases.as<uint8_t>(L.cursor + 64 + 64);  // (upload() asks for the same sizes again)
     const uint32_t nReads = locus_read_begin[n_loci];
     dOff   = bReadOff.as<uint64_t>(size_t(nReads) + 1);
     dBegin = bLocusBegin.as<uint32_t>(size_t(n_loci) + 1);
-    resetChunkCounter(copyStream);
+    chunks.reset(copyStream);
     rt::sync();
     {
       // the per-read offsets (6.4 MB for the metric's batch) and the locus table go first, on the chunks' own stream: on another stream,
@@ -1015,12 +818,10 @@ struct AsmStage {
       rt::ScopedStream onCopy(copyStream);
       rt::h2d(dOff, read_off, sizeof(uint64_t) * (size_t(nReads) + 1));
       rt::h2d(dBegin, locus_read_begin, sizeof(uint32_t) * (size_t(n_loci) + 1));
-      evPreSmall.record();
+      chunks.evPreSmall.record();
     }
-    queueChunks(preLayout, bases, copyStream);
-    preStreamed = true;
-    preLoci     = n_loci;
-    return true;
+    queueBases(L, bases, copyStream);
+    return ticket;
   }
 
   /// uploadStreamed() for packed piles: per chunk the slices of the five pile arrays (codes, N masks, read lengths and the two
@@ -1028,18 +829,17 @@ struct AsmStage {
   /// locus' slices through three per-chunk shifts (AsmParams::pl_chunk_shift).  Only the locus table goes first.
   void uploadPilesStreamed(const manta_packed_piles_t& pl, rt::Stream& copyStream)
   {
-    chunkLoci = std::max<uint32_t>(1, (nLoci + streamChunks() - 1) / streamChunks());
-    const uint32_t nChunks = (nLoci + chunkLoci - 1) / chunkLoci;
+    const ChunkStream::Chunking k(nLoci);
     struct Piece {
       uint32_t r0, r1;
       uint64_t c0, c1, m0, m1, dr, dc, dm;
     };
-    std::vector<Piece>    pc(nChunks);
-    std::vector<uint64_t> shifts(3 * kStreamChunks, 0);
+    std::vector<Piece>    pc(k.nChunks);
+    std::vector<uint64_t> shifts(3 * ChunkStream::kStreamChunks, 0);
     uint64_t              curR = 0, curC = 0, curM = 0;
     auto                  lineUp = [](uint64_t v) { return (v + 63) & ~uint64_t(63); };  // 64 elements >= one 128-byte line for every array
-    for (uint32_t c = 0; c < nChunks; ++c) {
-      const uint32_t l0 = c * chunkLoci, l1 = std::min(nLoci, l0 + chunkLoci);
+    for (uint32_t c = 0; c < k.nChunks; ++c) {
+      const uint32_t l0 = c * k.chunkLoci, l1 = std::min(nLoci, l0 + k.chunkLoci);
       Piece&         q(pc[c]);
       q.r0 = pl.locus_read_begin[l0], q.r1 = pl.locus_read_begin[l1];
       q.c0 = pl.read_code_off[q.r0], q.c1 = pl.read_code_off[q.r1];
@@ -1059,40 +859,28 @@ struct AsmStage {
     dPlMaskOff = bPlMaskOff.as<uint64_t>(curR + 64);
     plBytes    = 0;
     upload(nullptr, nullptr, pl.locus_read_begin);  // allocations + order, word lengths, growth schedule, locus table
-    dPlShift = bPlShift.as<uint64_t>(3 * kStreamChunks);
-    rt::h2d(dPlShift, shifts.data(), sizeof(uint64_t) * 3 * kStreamChunks);
-    if (!dChunksDone) dChunksDone = static_cast<uint32_t*>(rt::dmallocFine(64));
-    uint32_t* ids = pChunkIds.as<uint32_t>(kStreamChunks + 1);
-    for (uint32_t c = 0; c <= kStreamChunks; ++c) ids[c] = c;
-    {  // a call that failed half way may have left counter bumps queued on the copy stream: none may land after the reset
-      rt::ScopedStream onCopy(copyStream);
-      rt::sync();
-    }
-    rt::h2d(dChunksDone, ids, sizeof(uint32_t));  // = 0
+    chunks.begin(ChunkStream::Mode::Piles, k, shifts.data());
+    chunks.reset(copyStream);
     rt::sync();
-    {
-      rt::ScopedStream onCopy(copyStream);
-      for (uint32_t c = 0; c < nChunks; ++c) {
-        const Piece&   q(pc[c]);
-        const uint64_t nR = q.r1 - q.r0;
-        rt::h2d(dPlLen + q.dr, pl.read_len + q.r0, sizeof(uint32_t) * nR);
-        rt::h2d(dPlCodeOff + q.dr, pl.read_code_off + q.r0, sizeof(uint64_t) * (nR + 1));
-        rt::h2d(dPlMaskOff + q.dr, pl.read_mask_off + q.r0, sizeof(uint64_t) * (nR + 1));
-        rt::h2d(dPlCodes + q.dc, pl.codes + q.c0, sizeof(uint32_t) * (q.c1 - q.c0));
-        rt::h2d(dPlMask + q.dm, pl.nmask + q.m0, sizeof(uint32_t) * (q.m1 - q.m0));
-        if (!rt::streamWrite32(dChunksDone, c + 1)) rt::h2d(dChunksDone, ids + c + 1, sizeof(uint32_t));
-        plBytes += 4 * (q.c1 - q.c0) + 4 * (q.m1 - q.m0) + 20ull * nR;
-      }
-    }
-    streaming       = true;
-    streamingPiles  = true;
+    chunks.queue(k.nChunks, copyStream, [&](uint32_t c) {
+      const Piece&   q(pc[c]);
+      const uint64_t nR = q.r1 - q.r0;
+      rt::h2d(dPlLen + q.dr, pl.read_len + q.r0, sizeof(uint32_t) * nR);
+      rt::h2d(dPlCodeOff + q.dr, pl.read_code_off + q.r0, sizeof(uint64_t) * (nR + 1));
+      rt::h2d(dPlMaskOff + q.dr, pl.read_mask_off + q.r0, sizeof(uint64_t) * (nR + 1));
+      rt::h2d(dPlCodes + q.dc, pl.codes + q.c0, sizeof(uint32_t) * (q.c1 - q.c0));
+      rt::h2d(dPlMask + q.dm, pl.nmask + q.m0, sizeof(uint32_t) * (q.m1 - q.m0));
+      plBytes += 4 * (q.c1 - q.c0) + 4 * (q.m1 - q.m0) + 20ull * nR;
+    });
   }
 
-  void upload(const uint8_t* bases, const uint64_t* read_off, const uint32_t* locus_read_begin)
+  void upload(const uint8_t* bases, const uint64_t* read_off, const uint32_t* locus_read_begin) { upload(bases, read_off, locus_read_begin, nBases); }
+  /// `arenaBases`: bytes of the read-base arena to allocate (a streamed upload pads its chunks)
+  void upload(const uint8_t* bases, const uint64_t* read_off, const uint32_t* locus_read_begin, const uint64_t arenaBases)
   {
     if (bases) dPlCodes = nullptr;
-    streaming = streamingPiles = false;
-    dBases  = bBases.as<uint8_t>(nBases + 64);
+    chunks.off();
+    dBases  = bBases.as<uint8_t>(arenaBases + 64);
     dOff    = bReadOff.as<uint64_t>(nReadsTotal + 1);
     dBegin  = bLocusBegin.as<uint32_t>(nLoci + 1);
     dLoci   = bLoci.as<AsmLocusOut>(nLoci);
@@ -1190,10 +978,7 @@ struct AsmStage {
     P.pl_read_len    = dPlLen;
     P.pl_code_off    = dPlCodeOff;
     P.pl_mask_off    = dPlMaskOff;
-    P.upload_chunks_done = streaming ? dChunksDone : nullptr;
-    P.chunk_shift        = (streaming && !streamingPiles) ? dStream + 1 : nullptr;
-    P.pl_chunk_shift     = streamingPiles ? dPlShift : nullptr;
-    P.chunk_loci         = streaming ? chunkLoci : 0;
+    chunks.fill(P);
     P.reserved2          = 0;
     P.small_min_seed_reads = smallMinSeedReads;
     P.small_max_iterations = smallMaxIterations;
@@ -1212,7 +997,7 @@ struct AsmStage {
     // workgroup slot while a persistent kernel runs -- the general kernel leaves one slot free on a quarter of the CUs (the fast
     // kernel's three workgroups per CU leave plenty)
     int g = grid;
-    if (streaming && g >= ctx->cuCount * 16) g = rt::roundGrid(g - ctx->cuCount);
+    if (chunks.active() && g >= ctx->cuCount * 16) g = rt::roundGrid(g - ctx->cuCount);
     P.lds_bytes = ASM_LDS_BYTES;
     if (useFast) {
       using namespace manta_dev;
@@ -1264,7 +1049,7 @@ struct AsmStage {
       // free (streamFreeSlots) -- without them the copies never run and the persistent workgroups wait for their chunks forever
       // (seen on hardware, round 4)
       int gf = gridFast;
-      if (streaming && gf >= ctx->cuCount * 2) gf -= streamFreeSlots(ctx->cuCount);
+      if (chunks.active() && gf >= ctx->cuCount * 2) gf -= ChunkStream::streamFreeSlots(ctx->cuCount);
       // (the instantiation by the longest first word length among the loci of this launch: keys of 2 / 4 / 8 dwords)
       if (!fastIds.empty()) {
         uint32_t firstWl = opt.min_word_length;
@@ -1315,7 +1100,7 @@ struct AsmStage {
         B.G.cws        = bCwsBig.as<uint8_t>(cwsStrideBig * uint64_t(maxGridBig));
         B.G.cws_stride = cwsStrideBig;
         int gb = gridBig;
-        if (streaming && gb >= ctx->cuCount) gb -= streamFreeSlots(ctx->cuCount);  // (as above: one workgroup owns a CU's whole LDS)
+        if (chunks.active() && gb >= ctx->cuCount) gb -= ChunkStream::streamFreeSlots(ctx->cuCount);  // (as above: one workgroup owns a CU's whole LDS)
         // (the instantiation by the longest word length the kernel may meet: the first one without the rounds, any of them with)
         uint32_t firstWl = bigRounds ? opt.max_word_length : opt.min_word_length;
         if (!locusMinWl.empty()) {
@@ -1947,11 +1732,7 @@ struct GateLock {
 template <typename Pipe>
 void drainCopyStream(Pipe* b) noexcept
 {
-  try {
-    rt::ScopedStream onCopy(b->copy);
-    rt::sync();
-  } catch (...) {
-  }
+  ChunkStream::drain(&b->copy);
 }
 
 /// one run of a fused pipeline (api.cpp); `gates` = the stage gates of a whole-batch call with several workers, else nullptr

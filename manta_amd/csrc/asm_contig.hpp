@@ -18,7 +18,6 @@
 // loci -- the L2's atomic rate, not the waves in flight, set the kernel's speed.)
 #pragma once
 #ifdef MANTA_WAVE_EMU
-#include <map>
 #include <set>
 #endif
 #include "asm_lds.hpp"
@@ -391,7 +390,9 @@ struct LdsContig {
   /// word that its stretch's walk did not consume simply ends the replay and heads the next list.
 #ifdef MANTA_WAVE_EMU
   struct Dbg { std::set<unsigned> looked, listed, dropped, walked, evicted; };
-  static Dbg& dbg() { static Dbg d; return d; }
+  static Dbg& dbg() { static thread_local Dbg d; return d; }  // (per OS thread: the workers of a batch call run their kernels side by side)
+  static bool emuWhy() { static const bool on = std::getenv("MANTA_EMU_WHY") != nullptr; return on; }
+  static bool emuRoundTrace() { static const bool on = std::getenv("MANTA_EMU_ROUND_TRACE") != nullptr; return on; }
 #endif
   // Round 6 ("the walk rounds of a tandem pile's passes"; counted with MANTA_EMU_WHY on the emulator):
   //   PLAIN  the first PLAIN looked-at words are all kept, duplicates of a stretch or not.  Used when MANTA_STRETCH_LATE or fewer candidates
@@ -441,7 +442,7 @@ struct LdsContig {
     uint64_t keepM[WIN];
     for (unsigned h = 0; h < WIN; ++h) keepM[h] = wv::ballot(ent[h] != ASM_NONE && !dup[h]);
 #ifdef MANTA_WAVE_EMU
-    if (std::getenv("MANTA_EMU_WHY")) {
+    if (emuWhy()) {
       for (unsigned h = 0; h < WIN; ++h)
         if (ent[h] != ASM_NONE) {
           dbg().looked.insert(ent[h]);
@@ -823,7 +824,7 @@ struct LdsContig {
       findSlots();
       uint64_t miss = wv::ballot(lane < nL && slot == LG_NO_SLOT);
 #ifdef MANTA_WAVE_EMU
-      if (std::getenv("MANTA_EMU_ROUND_TRACE") && lane == 0) {
+      if (emuRoundTrace() && lane == 0) {
         std::fprintf(stderr, "  replay list (%u cands so far, nEligible %u, nFat %u): %u entries, missing mask %016llx; entries (id:count):", nCand, nEligible, nFat, nL, (unsigned long long)miss);
         for (unsigned i = 0; i < nL && i < 24; ++i) std::fprintf(stderr, " %u:%u%s", unsigned(tent[i]), R::cnt(nodes[tent[i]]), ((miss >> i) & 1u) ? "*" : "");
         std::fprintf(stderr, "\n");
@@ -937,7 +938,7 @@ struct LdsContig {
     slotNode[lane] = uint16_t(LG_NO_SLOT);
     uint64_t cached = 0, accAll = 0;
 #ifdef MANTA_WAVE_EMU
-    if (lane == 0) dbg() = Dbg();
+    if (emuWhy() && lane == 0) dbg() = Dbg();
 #endif
     {  // round 0: the first seed (id 0) and beside it graph_big_kernel's speculation list
       const uint16_t* spec = gSpecList();
@@ -972,7 +973,7 @@ struct LdsContig {
       }
       tick(7);
 #ifdef MANTA_WAVE_EMU
-      if (std::getenv("MANTA_EMU_WHY") && lane == 0) {
+      if (emuWhy() && lane == 0) {
         const char* why = dbg().evicted.count(nd) ? "walked-then-evicted" : dbg().walked.count(nd) ? "walked(?)" : dbg().listed.count(nd) ? "listed-not-walked" : dbg().dropped.count(nd) ? "dropped-as-stretch-duplicate" : dbg().looked.count(nd) ? "looked" : "outside-every-window";
         std::fprintf(stderr, "WHY round at %u cands: seed %u count %u: %s\n", nCand, nd, R::cnt(nodes[nd]), why);
       }
@@ -980,7 +981,7 @@ struct LdsContig {
       // ---- a walk round: the next seed and, beside it, the words most likely to follow it ----
       unsigned       nL   = stretchSeedList((capCand - nCand <= MANTA_STRETCH_LATE) ? unsigned(MANTA_STRETCH_PLAIN) : 0u);
 #ifdef MANTA_WAVE_EMU
-      if (std::getenv("MANTA_EMU_WHY") && lane < nL) dbg().listed.insert(unsigned(tent[lane]));
+      if (emuWhy() && lane < nL) dbg().listed.insert(unsigned(tent[lane]));
 #endif
       const unsigned node = (lane < nL) ? unsigned(tent[lane]) : ASM_NONE;
       unsigned       slot = LG_NO_SLOT;
@@ -995,7 +996,7 @@ struct LdsContig {
       findSlots();
       uint64_t miss = wv::ballot(lane < nL && slot == LG_NO_SLOT);
 #ifdef MANTA_WAVE_EMU
-      if (std::getenv("MANTA_EMU_ROUND_TRACE") && lane == 0) {
+      if (emuRoundTrace() && lane == 0) {
         std::fprintf(stderr, "  walk round (%u cands so far): list of %u, missing %016llx; entries (id:count):", nCand, nL, (unsigned long long)miss);
         for (unsigned i = 0; i < nL && i < 24; ++i) std::fprintf(stderr, " %u:%u%s", unsigned(tent[i]), R::cnt(nodes[tent[i]]), ((miss >> i) & 1u) ? "*" : "");
         std::fprintf(stderr, "\n");
@@ -1050,7 +1051,7 @@ struct LdsContig {
         // (making room for the first few missing entries only, at the cost of the cached walks latest in seed order, was tried: fewer
         // walks, the same number of rounds -- the single-read words' walks it gives up are the ones needed last)
 #ifdef MANTA_WAVE_EMU
-        if (std::getenv("MANTA_EMU_WHY") && !((accAll >> lane) & 1u) && slotNode[lane] != LG_NO_SLOT) dbg().evicted.insert(unsigned(slotNode[lane]));
+        if (emuWhy() && !((accAll >> lane) & 1u) && slotNode[lane] != LG_NO_SLOT) dbg().evicted.insert(unsigned(slotNode[lane]));
 #endif
         if (!((accAll >> lane) & 1u)) slotNode[lane] = uint16_t(LG_NO_SLOT);
         cached = accAll;
@@ -1071,7 +1072,7 @@ struct LdsContig {
         slot           = tbl[rnk];
         slotNode[slot] = uint16_t(node);
 #ifdef MANTA_WAVE_EMU
-        if (std::getenv("MANTA_EMU_WHY")) dbg().walked.insert(node);
+        if (emuWhy()) dbg().walked.insert(node);
 #endif
       }
       uint64_t walkMask = 0;

@@ -4,7 +4,7 @@ lengths per locus go through the same launch."""
 import numpy as np
 import pytest
 
-from manta_amd._capi import BatchOutput, SmallSvBatch, SpanningBatch, pack_spanning, small_sv_text
+from manta_amd._capi import BatchOutput, MantaError, SmallSvBatch, SpanningBatch, pack_spanning, small_sv_text
 from oracle_lib import asm_opts
 from synth import breakend_locus, config2_batch, unpack_locus
 from test_spanning_pipeline import SC as SPAN_SC, oracle_locus
@@ -16,8 +16,8 @@ def small_batch(n, seed):
     return config2_batch(n, seed=seed, n_reads=20, read_len=80, ref_len=500)
 
 
-def check_smallsv(lib, oracle, n, block, workers, mixed, streamed=True):
-    batch = small_batch(n, 4242)
+def check_smallsv(lib, oracle, n, block, workers, mixed, streamed=True, seed=4242):
+    batch = small_batch(n, seed)
     batch = batch[:5] + (np.tile(np.array([40, 40, 200, 200], dtype=np.int32), (n, 1)),)
     opts = asm_opts(minWordLength=25, maxWordLength=45)
     min_wl = max_wl = None
@@ -122,6 +122,34 @@ def test_gpu_batch_overlap_knobs(gpu, oracle, monkeypatch):
     overlap_knobs(gpu, oracle, monkeypatch, 300, block=300, workers=1)
     monkeypatch.setenv("MANTA_AMD_HOST_PARTS", "4")
     overlap_knobs(gpu, oracle, monkeypatch, 200, block=64, workers=3)
+
+
+def fail_then_knob(lib, oracle, monkeypatch, n):
+    """a streamed upload that fails behind its early stream leaves nothing to the next call on the same pooled pipeline: call 1 has two
+    read offsets swapped inside a locus (the early stream queues its chunks, plan() refuses); call 2, another batch of the same size with
+    the early stream switched off, and call 3 with it on again, must each assemble their own bases"""
+    opts = asm_opts(minWordLength=25, maxWordLength=45)
+    bases, read_off, *rest = small_batch(n, 5151)
+    read_off = read_off.copy()
+    r = 20 * (n // 2) + 7  # strictly inside locus n // 2: every chunk boundary stays monotone
+    read_off[[r, r + 1]] = read_off[[r + 1, r]]
+    out = BatchOutput(lib, "smallsv", n, 10, 1 << 20, 1 << 16, 1 << 18)
+    with pytest.raises(MantaError) as err:
+        lib.smallsv_batch(opts, SCORES, -100, (bases, read_off, *rest), out, block_loci=n, n_workers=1, streamed_upload=True)
+    assert err.value.code == -1 and "read_off not monotone" in str(err.value)  # MANTA_E_INVALID_ARG
+    monkeypatch.setenv("MANTA_AMD_NO_EARLY_STREAM", "1")
+    check_smallsv(lib, oracle, n, block=n, workers=1, mixed=False, seed=6262)
+    monkeypatch.delenv("MANTA_AMD_NO_EARLY_STREAM")
+    check_smallsv(lib, oracle, n, block=n, workers=1, mixed=False, seed=6262)
+
+
+def test_emulated_batch_failed_early_stream_leaves_no_state(emu, oracle, monkeypatch):
+    fail_then_knob(emu, oracle, monkeypatch, 10)  # one locus per chunk
+
+
+@pytest.mark.gpu
+def test_gpu_batch_failed_early_stream_leaves_no_state(gpu, oracle, monkeypatch):
+    fail_then_knob(gpu, oracle, monkeypatch, 40)  # 14 chunks of 3 loci, the last one short
 
 
 @pytest.mark.gpu

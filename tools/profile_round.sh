@@ -26,7 +26,7 @@ timeout -s KILL 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace_ste
 if [ "$2" = "spanning" ]; then
   timeout 600 $B --workload spanning --steps 2 --warmup 1 --full > $O/bench_spanning_line.json 2> $O/bench_spanning.err
   timeout -s KILL 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_spanning -o bench -- $B --workload spanning --steps 2 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
-  # (the config-5 shape's traffic counters: tools/gpu_r6_final.sh, on the 2 048 digest loci with the blocking upload -- a streamed upload under
+  # (the config-5 shape's traffic counters: gpu_r6_final.sh in git history at 0635c77, on the 2 048 digest loci with the blocking upload -- a streamed upload under
   #  rocprofv3 --pmc never finishes: dispatches are serialised, the copy kernels wait for the assembler, which waits for its chunks)
 fi
 if [ "$2" = "spanning" ] || [ "$3" = "read_class" ] || [ "$2" = "read_class" ]; then

@@ -104,10 +104,10 @@ if sper:
     span_loci = 65536
     if os.path.exists(sp) and os.path.getsize(sp):
         span_loci = json.loads(open(sp).read().strip().splitlines()[-1])["config"]["loci_per_gpu"]
-    marker = os.path.join(src, "spanning_pmc_loci.txt")  # (counter passes on fewer loci than the bench line: tools/gpu_r4_q.sh)
+    marker = os.path.join(src, "spanning_pmc_loci.txt")  # (counter passes on fewer loci than the bench line: gpu_r4_q.sh, in git history at 0635c77)
     if os.path.exists(marker):
         span_loci = int(open(marker).read().split()[0])
-    st = {"loci": span_loci, "workload": "spanning", "source": traffic["source"] + " / tools/gpu_r4_q.sh", "date": traffic["date"],
+    st = {"loci": span_loci, "workload": "spanning", "source": traffic["source"] + " / gpu_r4_q.sh (git history at 0635c77)", "date": traffic["date"],
           "note": "HBM-side bytes of ONE step of `bench.py --workload spanning --loci <loci>` = (FETCH_SIZE + WRITE_SIZE) KiB * 1024 per kernel, rocprofv3 --pmc, "
                   "separate passes, raw.  `loci` is the size of the counter passes' block: under the profiler the bench line's 65 536-locus block ran into "
                   "the passes' time limit, so they ran on fewer loci (per-locus traffic is what carries over)"}

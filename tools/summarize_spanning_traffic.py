@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gpurun_out/<dir>/spanning_pmc_{fetch,write}/ (tools/gpu_r5_w.sh: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of
+"""<output dir>/spanning_pmc_{fetch,write}/ (written by gpu_r5_w.sh, in git history at 0635c77: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of
 `bench.py --workload spanning --loci N --steps 1 --warmup 0`) -> profiles/traffic_spanning.json: HBM-side bytes per kernel, summed over
 ALL launches of the step (the big class launches its three kernels once per word length)."""
 import collections, csv, json, os, sys
@@ -18,7 +18,7 @@ for which in ("fetch", "write"):
         k = short(row["Kernel_Name"])
         if "rocclr" not in k:
             tot[k] += float(row["Counter_Value"]) * 1024
-st = {"loci": loci, "workload": "spanning", "source": "tools/gpu_r6_final.sh (builder-run counter passes on the final build, not the driver's run)",
+st = {"loci": loci, "workload": "spanning", "source": "gpu_r6_final.sh, in git history at 0635c77 (builder-run counter passes on the final build, not the driver's run)",
       "date": __import__("datetime").date.today().isoformat(),
       "note": "HBM-side bytes of ONE step of `bench.py --workload spanning --loci <loci>` = (FETCH_SIZE + WRITE_SIZE) KiB * 1024 per kernel, rocprofv3 --pmc, "
               "separate passes, raw, summed over all launches of the step (graph_big / repeat_big / contig_big: one launch per word length).  Counter "

@@ -331,31 +331,34 @@ inline size_t workspaceBudget(const size_t capBytes)
   return std::min<size_t>(freeNow / 2 / size_t(live), capBytes);
 }
 
-/// plan()'s inner loops over one locus' reads: dwords of 2-bit codes (16 bases each) and the longest read (all ones: a negative step /
-/// a read of 4 G bases).  The second form is the first compiled for AVX2 -- the host translation units are built for baseline x86-64,
-/// where the loop stays scalar (~1.1 ns per read; the metric's batch has 800 k) -- and is taken where the CPU has it.
+/// plan()'s inner loops over one locus' reads: dwords of 2-bit codes (16 bases each), dwords of the N bitmap (32 bases each) and the
+/// longest read (all ones: a negative step / a read of 4 G bases).  The second form is the first compiled for AVX2 -- the host
+/// translation units are built for baseline x86-64, where the loop stays scalar (~1.1 ns per read; the metric's batch has 800 k) -- and
+/// is taken where the CPU has it.
 #define MANTA_SCAN_OFFSETS_BODY                                                      \
-  uint64_t w = 0, hi = 0;                                                            \
+  uint64_t w = 0, mw = 0, hi = 0;                                                    \
   uint32_t m = 0;                                                                    \
   for (uint32_t i = 0; i < n; ++i) {                                                 \
     const uint64_t len = o[i + 1] - o[i];                                            \
     w += (len + 15) >> 4;                                                            \
+    mw += (len + 31) >> 5;                                                           \
     hi |= len >> 32;                                                                 \
     const uint32_t l32 = uint32_t(len);                                              \
     m                  = m > l32 ? m : l32;                                          \
   }                                                                                  \
   wOut       = w;                                                                    \
+  mwOut      = mw;                                                                   \
   longestOut = hi ? ~uint64_t(0) : uint64_t(m);
-inline void scanOffsetsBase(const uint64_t* o, const uint32_t n, uint64_t& wOut, uint64_t& longestOut) { MANTA_SCAN_OFFSETS_BODY }
+inline void scanOffsetsBase(const uint64_t* o, const uint32_t n, uint64_t& wOut, uint64_t& mwOut, uint64_t& longestOut) { MANTA_SCAN_OFFSETS_BODY }
 #if defined(__x86_64__) && !defined(MANTA_NO_AVX2_SCAN)
-__attribute__((target("avx2"))) inline void scanOffsetsAvx2(const uint64_t* o, const uint32_t n, uint64_t& wOut, uint64_t& longestOut) { MANTA_SCAN_OFFSETS_BODY }
+__attribute__((target("avx2"))) inline void scanOffsetsAvx2(const uint64_t* o, const uint32_t n, uint64_t& wOut, uint64_t& mwOut, uint64_t& longestOut) { MANTA_SCAN_OFFSETS_BODY }
 inline bool hostHasAvx2()
 {
   static const bool has = __builtin_cpu_supports("avx2") != 0;
   return has;
 }
 #else
-inline void scanOffsetsAvx2(const uint64_t* o, const uint32_t n, uint64_t& wOut, uint64_t& longestOut) { MANTA_SCAN_OFFSETS_BODY }
+inline void scanOffsetsAvx2(const uint64_t* o, const uint32_t n, uint64_t& wOut, uint64_t& mwOut, uint64_t& longestOut) { MANTA_SCAN_OFFSETS_BODY }
 inline bool hostHasAvx2() { return false; }
 #endif
 #undef MANTA_SCAN_OFFSETS_BODY
@@ -522,10 +525,10 @@ struct AsmStage {
             return;
           }
           // branch-free inner loops (they vectorise): a negative step shows up as a huge unsigned length in `longest`
-          uint64_t b = 0, w = 0, longest = 0;
+          uint64_t b = 0, w = 0, mw = 0, longest = 0;
           if (read_off) {
             const uint64_t* o = read_off + rb;
-            (avx2 ? scanOffsetsAvx2 : scanOffsetsBase)(o, re - rb, w, longest);
+            (avx2 ? scanOffsetsAvx2 : scanOffsetsBase)(o, re - rb, w, mw, longest);
             b = o[re - rb] - o[0];
           } else {
             const uint32_t* o = read_len + rb;
@@ -533,17 +536,19 @@ struct AsmStage {
               const uint64_t len = o[i];
               b += len;
               w += (len + 15) >> 4;
+              mw += (len + 31) >> 5;
               longest = std::max(longest, len);
             }
           }
           w += re - rb;
+          mw += re - rb;
           if (longest > 0xffffffffull) {  // (also: a single read of 4 G bases is not a read)
             p.bad = 2;
             return;
           }
           p.maxReadLen = std::max<uint32_t>(p.maxReadLen, uint32_t(longest));
           cost[l] = b * uint64_t(re - rb);
-          if ((re - rb) + 2 * maxAsm <= manta_dev::LG_MAX_READS && w + 2 <= manta_dev::LG_MAX_PILE) {
+          if (manta_dev::lgPileFits(re - rb, maxAsm, w, mw, longest)) {  // (the test LdsGraph::pack() makes on the device)
             p.ldsFit++;
             cost[l] |= uint64_t(1) << 63;  // (marks the locus for the split below; reads x bases stays far below 2^62)
           } else if ((re - rb) + 2 * maxAsm <= manta_dev::LGL_MAX_READS && w + 2 <= manta_dev::LGL_MAX_PILE + 2 &&

@@ -155,6 +155,18 @@ WV_HD uint64_t lgSlabBytes(const unsigned nNodes, const unsigned nFat, const uns
 {
   return lgSlab(nNodes, nFat, codeWords).total;
 }
+/// The pile-size half of the small class' envelope, ONE function for LdsGraph::pack() and for the host's planning pass (AsmStage::plan):
+/// a pile the device would refuse for its size must not be marked for this class (it would end on assemble_kernel although the big
+/// class takes it).  cw / mw: the reads' code / N-bitmap dwords with their padding dword each, sum(ceil(len / 16)) + nReads and
+/// sum(ceil(len / 32)) + nReads; longest: the longest read (the descriptors hold 16 bits).
+/// (mw >= cw / 2, so the LG_BUDGET line refuses every pile from cw ~ 2000 on: LG_MAX_PILE alone never binds.)
+WV_HD bool lgPileFits(const uint64_t nReads, const uint64_t maxAssemblyCount, const uint64_t cw, const uint64_t mw, const uint64_t longest)
+{
+  if (nReads + 2 * maxAssemblyCount > LG_MAX_READS) return false;
+  if (longest > 0xffffu || cw + 2 > LG_MAX_PILE) return false;
+  const uint64_t cwPad = (cw + 2 + 3) & ~uint64_t(3), mwPad = (mw + 2 + 3) & ~uint64_t(3);
+  return LG_OFF_DYN + 4 * (cwPad + mwPad) <= LG_BUDGET;
+}
 
 // contig_kernel LDS map
 static const unsigned CK_OFF_HDR    = 0;     // LgHdr
@@ -661,7 +673,7 @@ struct LdsGraph {
   {
     const unsigned rBegin = P.locus_read_begin[locus], rEnd = P.locus_read_begin[locus + 1];
     nNormal               = rEnd - rBegin;
-    if (nNormal + 2 * P.opt.maxAssemblyCount > LG_MAX_READS) return false;
+    if (!lgPileFits(nNormal, P.opt.maxAssemblyCount, 0, 0, 0)) return false;  // (the read count, before the descriptors are written)
     W = (nNormal + 2 * P.opt.maxAssemblyCount + 63) / 64;
     if (W == 0) W = 1;
     const uint64_t plR = plShift(locus, 0), plC = plShift(locus, 1), plM = plShift(locus, 2);
@@ -694,9 +706,8 @@ struct LdsGraph {
       mw += wv::readlane(sm, 63);
       nb += wv::readlane(sb, 63);
     }
-    if (wv::any(tooLong) || cw + 2 > LG_MAX_PILE) return false;
+    if (!lgPileFits(nNormal, P.opt.maxAssemblyCount, cw, mw, wv::any(tooLong) ? 0x10000u : 0u)) return false;
     const unsigned cwPad = (cw + 2 + 3) & ~3u, mwPad = (mw + 2 + 3) & ~3u;
-    if (LG_OFF_DYN + 4 * (cwPad + mwPad) > LG_BUDGET) return false;
     codeWords = cw + 2;
     nmask     = codes + cwPad;
     for (unsigned i = tid(); i < mw + 2; i += nThreads()) nmask[i] = 0;

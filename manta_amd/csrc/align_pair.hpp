@@ -8,20 +8,39 @@
 // v_pk_add_i16 / v_pk_max_i16 with the low half of every register belonging to task A and the high half to task B: the same
 // instruction stream, half the instructions per cell.
 //
-// Exactness.  States live in the x8 domain (value * 8, index bits clear).  The reference's finite sentinel badVal = -10000
-// becomes INT16_MIN = -4096 * 8, and every addition SATURATES, so sentinel-derived cells stay at or just above it.  A cell
-// whose value derives from the boundary row / column without the sentinel ("real") is bounded below by
+// Representation.  The index of a candidate is always the index of the state it is made from (match takes the diagonal cell's
+// five states in order; delete takes match, delete, insert, -, jumpIns; insert takes match, -, insert; jumpDel match, -, insert,
+// jump, jumpIns; jumpIns match, -, -, -, jumpIns).  A state is therefore STORED with its own tag, value * 8 | (7 - state): a
+// candidate is the stored state plus the score alone, and a candidate that adds no score is the stored state itself.  The
+// arg-max carries the winner's tag, which is the cell's pointer; the next state is (max & ~7) + (score * 8 + its tag) for
+// match, delete and insert -- the tag rides in the constant the add needs anyway -- and (max & ~7) | tag for the two jump states.
+//
+// Exactness.  The reference's finite sentinel badVal = -10000 becomes INT16_MIN = -4096 * 8, and every addition SATURATES, so
+// sentinel-derived cells stay at or just above it.  A cell whose value derives from the boundary row / column without the
+// sentinel ("real") is bounded below by
 //     Q * min(mismatch, offEdge, 0) + open + extend + largeIndel   (the all-mismatch diagonal; a gap state always has the
 //                                                                   fresh-open candidate of its neighbour)
 // and sentinel-derived cells are bounded above by  -4096 + Q * max(match, 0).  pairEligible() admits an E bucket only when the
 // first bound clears the second with a margin for every query the bucket can hold: then every arg-max among candidates that
 // include a real one picks the same winner as the reference's int arithmetic, and the traceback (which starts at a real cell
 // and follows winners) only ever reads such cells.  Pointers of sentinel-only cells may differ from the reference's; nothing
-// reads them.  The '='/'X' expansion and the traceback are align_kernel's own (Aligner<1, E, true>: the two tasks' cells
-// interleave in one slab, a task reads every second 16-bit word).
+// reads them.
+//   The tag inside the forming constant spends none of that margin.  With x a multiple of 8 and c8 = score * 8, a state formed as
+// sat(x + c8 + tag) equals sat(x + c8) | tag whenever x + c8 >= -32768, and is exactly -32768, tag bits clear, whenever
+// x + c8 < -32768 (then x + c8 + tag <= -32769 as well): value >> 3 is what it would be without the tag, in every cell.  The one
+// difference is the TAG of a state that saturated (and of the -32768 the table starts from and resets to): 0 where 7 - state is
+// meant.  Such a state is sentinel-derived by definition, a real state never comes within the margin of the floor.  A candidate
+// made from it is at most 7 units of the x8 domain -- less than one score unit -- BELOW what the tag would have made it, so it
+// can displace nothing that won before, and where it wins (all candidates sentinel-derived) the value is unchanged and only the
+// pointer of a sentinel-only cell differs.  For the same reason the candidates the reference holds at badVal (delete's index 3,
+// index 1 of insert, jumpDel and jumpIns) are not computed at all: they sit at the floor and could only ever set the pointer of
+// a cell whose other candidates all sit there too.
+//   The '='/'X' expansion and the traceback are align_kernel's own (Aligner<1, E, true>: the two tasks' cells interleave in one
+// slab, a task reads every second 16-bit word); the pointer layout is unchanged.
 //
 // Rows.  Both tasks sweep max(G_A, G_B) reference rows; the shorter one computes rows past its reference against base 0 (never a
-// match), its start candidates stop at its own last row.  Start candidates are tracked as in align_kernel (AlignerUtil.hpp:53-67).
+// match), its start candidates stop at its own last row.  Start candidates follow AlignerUtil.hpp:53-67, with nothing lane-masked
+// on the per-step path: see sweep().
 #pragma once
 #include "align_kernels.hpp"
 
@@ -64,30 +83,36 @@ struct PairAligner {
     const unsigned QA = TA.query_len, QB = TB.query_len, GA = TA.ref1_len, GB = TB.ref1_len;
     const unsigned G  = (GA > GB) ? GA : GB;
     const int      open = P.open, extend = P.extend, L = P.extra, offEdge = P.off_edge;
-    // packed constants (x8 domain; the index bits of candidate i are 7 - i)
-    const uint32_t cM0 = pk2(7), cD1 = pk2(6), cI2 = pk2(5), cJ3 = pk2(4), cJI4 = pk2(3);
-    const uint32_t cOpen0   = pk2(open * 8 + 7);        // match + open, candidate 0
-    const uint32_t cL0      = pk2(L * 8 + 7);           // match + L, candidate 0
-    const uint32_t cLmOpen2 = pk2((L - open) * 8 + 5);  // insert + L - open, candidate 2
-    const uint32_t cL4      = pk2(L * 8 + 3);           // jumpIns + L, candidate 4
-    const uint32_t cBad1 = pk2(PAIR_BAD8 + 6), cBad3 = pk2(PAIR_BAD8 + 4);
-    const uint32_t cExt     = pk2(extend * 8);
-    const uint32_t cMatch   = pk2(P.match * 8);
+    // packed constants (x8 domain).  A state carries its own tag (7 - state), which is the tag of every candidate made from it: the
+    // constants that CONSUME a state hold the score only, the constants that FORM a state hold the score and the state's tag
+    const uint32_t cOpen    = pk2(open * 8);        // match + open (delete, insert)
+    const uint32_t cL       = pk2(L * 8);           // match + L, jumpIns + L
+    const uint32_t cLmOpen  = pk2((L - open) * 8);  // insert + L - open
+    const uint32_t cExtD    = pk2(extend * 8 + (7 - ST_DELETE));
+    const uint32_t cExtI    = pk2(extend * 8 + (7 - ST_INSERT));
+    const uint32_t cMatch   = pk2(P.match * 8 + (7 - ST_MATCH));
     const uint32_t cMisDiff = pk2((P.mismatch - P.match) * 8);
+    const uint32_t tagJ = pk2(7 - ST_JUMP), tagJI = pk2(7 - ST_JUMPINS), tagM = pk2(7 - ST_MATCH);
     const uint32_t clrIdx = 0xfff8fff8u, idxBits = 0x00070007u, bad = pk2(PAIR_BAD8);
 
-    // traceback start candidates per task.  Rows at q == Q: one 32-bit key per task, (value x 8) << 16 | (0xffff - row), kept by
-    // a plain integer max on the lane that owns column Q: the higher value wins, among equal values the EARLIER row (the
-    // reference's strict '>' scan, AlignerUtil.hpp:53-67).  Off-edge candidates: the match states of a task's LAST row are
-    // captured into lastRow[] when a lane passes that row and evaluated once after the sweep.
+    // traceback start candidates per task.  Rows at q == Q: one 32-bit key per task, (tagged match state) << 16 | (0xffff - row),
+    // kept by a plain integer max: the higher value wins, among equal values the EARLIER row (the reference's strict '>' scan,
+    // AlignerUtil.hpp:53-67).  Only the key of lane lQ[h], the owner of column Q, is ever read, so every lane runs the same
+    // unmasked instructions on its own column eQ[h] and the one condition left -- the row of lane lQ[h] is a row of task h,
+    // t - lQ[h] <= G_h -- is wave-uniform.  Off-edge candidates: the match states of a task's LAST row are captured into
+    // lastRow[] in the steps in which some lane can be on that row (wave-uniform too) and evaluated once after the sweep.
     const unsigned Qs[2] = {QA, QB}, Gs[2] = {GA, GB};
-    unsigned       lQ[2], eQ[2];
+    unsigned       lQ[2], eQ[2], tKeyEnd[2];
     for (int h = 0; h < 2; ++h) {
-      lQ[h] = (Qs[h] - 1) / E;
-      eQ[h] = (Qs[h] - 1) % E;
+      lQ[h]      = (Qs[h] - 1) / E;
+      eQ[h]      = (Qs[h] - 1) % E;
+      tKeyEnd[h] = Gs[h] + lQ[h];
     }
-    int      rowKey[2] = {int(0x80000000u), int(0x80000000u)};
-    uint32_t lastRow[E];
+    uint32_t selQ[E];  // column e's match state supplies the low / high half of the key's value
+    for (int e = 0; e < E; ++e) selQ[e] = ((unsigned(e) == eQ[0]) ? 0x0000ffffu : 0u) | ((unsigned(e) == eQ[1]) ? 0xffff0000u : 0u);
+    const unsigned tCapLo = (GA < GB) ? GA : GB, tCapHi = G + 63;
+    int            rowKey[2] = {int(0x80000000u), int(0x80000000u)};
+    uint32_t       lastRow[E];
     for (int e = 0; e < E; ++e) lastRow[e] = bad;
     const uint32_t fcMask = (lane == 0) ? 0xffffffffu : 0u;  // column 1 of the query: gap states are reset (:130, :143, ...)
 
@@ -98,10 +123,10 @@ struct PairAligner {
       qc[e]            = a | (b << 16);
       const int row0   = int((q0 + 1) * unsigned(offEdge)) * 8;  // row 0 (GlobalAlignerImpl.hpp:66-80); beyond a task's query: unused columns
       for (int s = 0; s < NS; ++s) st[s][e] = bad;
-      st[ST_MATCH][e] = pk2(row0 < PAIR_BAD8 ? PAIR_BAD8 : row0);
+      st[ST_MATCH][e] = pk2(row0 < PAIR_BAD8 ? PAIR_BAD8 : row0 + (7 - ST_MATCH));
     }
     for (int s = 0; s < NS; ++s) lcur[s] = lprev[s] = bad;
-    lcur[ST_MATCH] = lprev[ST_MATCH] = 0;  // column 0, row 0
+    lcur[ST_MATCH] = lprev[ST_MATCH] = tagM;  // column 0, row 0
 
     unsigned curA = 0, curB = 0, nextA = 0, nextB = 0;
     {
@@ -111,7 +136,9 @@ struct PairAligner {
     }
     uint32_t rc = 0;  // this lane's reference symbols for its current row (A | B << 16)
 
-    const unsigned nSteps = G + 63;
+    // lane l computes row g in step g + l; the lanes behind the one that owns the longer query's last column hold no column anyone
+    // reads (their cells, pointers and lastRow[] are beyond both queries), so the sweep ends when that lane has passed row G
+    const unsigned nSteps = G + ((lQ[0] > lQ[1]) ? lQ[0] : lQ[1]);
     for (unsigned t = 1; t <= nSteps; ++t) {
       if (((t - 1) & 63) == 0) {
         curA              = nextA;
@@ -125,7 +152,7 @@ struct PairAligner {
       uint32_t incoming[NS];
       // lane 0 receives column 0 from the shift's fill value: rows >= 1 are (0, bad, bad, ..) (GlobalAlignerImpl.hpp:98-107); row 0 is
       // the initial lprev, and from row 2 on lprev is the previous step's lcur, i.e. the same fill
-      for (int s = 0; s < NS; ++s) incoming[s] = wv::shr1(st[s][E - 1], (s == ST_MATCH) ? 0u : bad);
+      for (int s = 0; s < NS; ++s) incoming[s] = wv::shr1(st[s][E - 1], (s == ST_MATCH) ? tagM : bad);
       const int g = int(t) - lane;  // this lane's row
       for (int s = 0; s < NS; ++s) {
         lprev[s] = lcur[s];
@@ -147,43 +174,48 @@ struct PairAligner {
         // substitution score per half: match where the symbols agree
         const uint32_t differ = wv::pk_min_u16(qc[e] ^ rc, 0x00010001u);
         const uint32_t sub8   = wv::pk_mad_u16(differ, cMisDiff, cMatch);
-        uint32_t       nv[NS], code;
-        {  // match: max5 over the diagonal cell's states
-          uint32_t m = wv::pk_max_i16(wv::pk_max_i16(wv::pk_add_sat_i16(diag[ST_MATCH], cM0), wv::pk_add_sat_i16(diag[ST_DELETE], cD1)), wv::pk_add_sat_i16(diag[ST_INSERT], cI2));
-          m          = wv::pk_max_i16(wv::pk_max_i16(m, wv::pk_add_sat_i16(diag[ST_JUMP], cJ3)), wv::pk_add_sat_i16(diag[ST_JUMPINS], cJI4));
+        uint32_t       nv[NS], tag[NS];
+        // (the candidates the reference sets to badVal -- delete's index 3, index 1 of insert, jumpDel and jumpIns -- are left out: they
+        // can only win a cell whose other candidates all sit at the floor, and then they change its pointer, never its value)
+        {  // match: max5 over the diagonal cell's states, each its own candidate
+          uint32_t m = wv::pk_max_i16(wv::pk_max_i16(diag[ST_MATCH], diag[ST_DELETE]), diag[ST_INSERT]);
+          m          = wv::pk_max_i16(wv::pk_max_i16(m, diag[ST_JUMP]), diag[ST_JUMPINS]);
           nv[ST_MATCH] = wv::pk_add_sat_i16(m & clrIdx, sub8);
-          code         = m & idxBits;
+          tag[ST_MATCH] = m & idxBits;
         }
         {  // delete (:121-135)
-          uint32_t m = wv::pk_max_i16(wv::pk_max_i16(wv::pk_add_sat_i16(up[ST_MATCH], cOpen0), wv::pk_add_sat_i16(up[ST_DELETE], cD1)), wv::pk_add_sat_i16(up[ST_INSERT], cI2));
-          m          = wv::pk_max_i16(wv::pk_max_i16(m, cBad3), wv::pk_add_sat_i16(up[ST_JUMPINS], cJI4));
-          uint32_t b = wv::pk_add_sat_i16(m & clrIdx, cExt);
+          uint32_t m = wv::pk_max_i16(wv::pk_max_i16(wv::pk_add_sat_i16(up[ST_MATCH], cOpen), up[ST_DELETE]), up[ST_INSERT]);
+          m          = wv::pk_max_i16(m, up[ST_JUMPINS]);
+          uint32_t b = wv::pk_add_sat_i16(m & clrIdx, cExtD);
           b = (b & ~fc) | (bad & fc);
           nv[ST_DELETE] = b;
-          code |= (m & idxBits) << 3;
+          tag[ST_DELETE] = m & idxBits;
         }
         {  // insert (:137-146)
-          uint32_t m = wv::pk_max_i16(wv::pk_max_i16(wv::pk_add_sat_i16(left[ST_MATCH], cOpen0), cBad1), wv::pk_add_sat_i16(left[ST_INSERT], cI2));
-          uint32_t b = wv::pk_add_sat_i16(m & clrIdx, cExt);
+          uint32_t m = wv::pk_max_i16(wv::pk_add_sat_i16(left[ST_MATCH], cOpen), left[ST_INSERT]);
+          uint32_t b = wv::pk_add_sat_i16(m & clrIdx, cExtI);
           b = (b & ~fc) | (bad & fc);
           nv[ST_INSERT] = b;
-          code |= (m & idxBits) << 6;
+          tag[ST_INSERT] = m & idxBits;
         }
         {  // jumpDel (:148-166)
-          uint32_t m = wv::pk_max_i16(wv::pk_max_i16(wv::pk_add_sat_i16(up[ST_MATCH], cL0), cBad1), wv::pk_add_sat_i16(up[ST_INSERT], cLmOpen2));
-          m          = wv::pk_max_i16(wv::pk_max_i16(m, wv::pk_add_sat_i16(up[ST_JUMP], cJ3)), wv::pk_add_sat_i16(up[ST_JUMPINS], cL4));
-          uint32_t b = m & clrIdx;
+          uint32_t m = wv::pk_max_i16(wv::pk_add_sat_i16(up[ST_MATCH], cL), wv::pk_add_sat_i16(up[ST_INSERT], cLmOpen));
+          m          = wv::pk_max_i16(wv::pk_max_i16(m, up[ST_JUMP]), wv::pk_add_sat_i16(up[ST_JUMPINS], cL));
+          uint32_t b = (m & clrIdx) | tagJ;
           b = (b & ~fc) | (bad & fc);
           nv[ST_JUMP] = b;
-          code |= (m & idxBits) << 9;
+          tag[ST_JUMP] = m & idxBits;
         }
         {  // jumpIns (:169-176)
-          uint32_t m = wv::pk_max_i16(wv::pk_max_i16(wv::pk_add_sat_i16(left[ST_MATCH], cL0), cBad1), wv::pk_add_sat_i16(left[ST_JUMPINS], cJI4));
-          uint32_t b = m & clrIdx;
+          uint32_t m = wv::pk_max_i16(wv::pk_add_sat_i16(left[ST_MATCH], cL), left[ST_JUMPINS]);
+          uint32_t b = (m & clrIdx) | tagJI;
           b = (b & ~fc) | (bad & fc);
           nv[ST_JUMPINS] = b;
-          code |= (m & idxBits) << 12;
+          tag[ST_JUMPINS] = m & idxBits;
         }
+        // the cell's pointers, 3 bits per state from bit 0 (match) up; 15 bits per half, so the shifts carry nothing across
+        uint32_t code = tag[NS - 1];
+        for (int s = NS - 2; s >= 0; --s) code = (code << 3) | tag[s];
         for (int s = 0; s < NS; ++s) {
           diag[s]  = up[s];
           left[s]  = nv[s];
@@ -198,16 +230,16 @@ struct PairAligner {
 #endif
 
       // traceback start candidates (see above)
-      {
+      if (t >= tCapLo && t <= tCapHi) {
         const uint32_t cap = ((unsigned(g) == GA) ? 0x0000ffffu : 0u) | ((unsigned(g) == GB) ? 0xffff0000u : 0u);
         for (int e = 0; e < E; ++e) lastRow[e] = (lastRow[e] & ~cap) | (st[ST_MATCH][e] & cap);
-        for (int h = 0; h < 2; ++h) {
-          uint32_t vM = st[ST_MATCH][0];
-          for (int e = 1; e < E; ++e) vM = (unsigned(e) == eQ[h]) ? st[ST_MATCH][e] : vM;
-          const int  key = int((uint32_t(half(vM, h)) << 16) | (0xffffu - unsigned(g)));
-          const bool on  = unsigned(lane) == lQ[h] && unsigned(g) <= Gs[h];
-          rowKey[h]      = imax(rowKey[h], on ? key : int(0x80000000u));
-        }
+      }
+      {
+        uint32_t vM = st[ST_MATCH][0];
+        for (int e = 1; e < E; ++e) vM = (st[ST_MATCH][e] & selQ[e]) | (vM & ~selQ[e]);
+        const uint32_t rowInv = 0xffffu - unsigned(g);
+        if (t <= tKeyEnd[0]) rowKey[0] = imax(rowKey[0], int((vM << 16) | rowInv));
+        if (t <= tKeyEnd[1]) rowKey[1] = imax(rowKey[1], int((vM & 0xffff0000u) | rowInv));
       }
     }
     for (int h = 0; h < 2; ++h) {
@@ -312,7 +344,7 @@ struct PairMultiParams {
   uint32_t        n_order;     ///< <= 6
   uint8_t         order[8];    ///< bucket indices in queue order
   uint8_t         e_of[8];     ///< their E
-  uint32_t        prio_work[3];  ///< a pair of at least this much work (E x (G + 64)) issues at priority 1 / 2 / 3 (s_setprio); 0 = never
+  uint32_t        prio_work[3];  ///< a pair of at least this much work (E x (G + 64): the step count's upper bound) issues at priority 1 / 2 / 3 (s_setprio); 0 = never
 };
 
 template <int E>
@@ -321,10 +353,16 @@ WV_DEV void runPairWidth(const AlignParams& A, const unsigned ta, const unsigned
   PairAligner<E>(A).run(A.tasks[ta], A.tasks[tb], A.results[ta], A.results[tb], haveB, slab);
 }
 
+// (waves per SIMD the register allocator is held to: at three the six inlined widths fit 149 VGPRs without a spill, at four 128 with
+// 15 spilled; two waves per SIMD already reach the issue ceiling, and the step measured 7.79-7.86 ms at three against 7.93-7.98 at
+// four.  The host's grid, smallsvAlignWavesPerCu() = 4 x this per CU, follows it; -DMANTA_PAIR_MULTI_OCC=4 is the A/B variant)
+#ifndef MANTA_PAIR_MULTI_OCC
+#define MANTA_PAIR_MULTI_OCC 3
+#endif
 #if !MANTA_TU_DEFINES(MANTA_TU_ALIGN_PAIR)
-WV_KERNEL_OCC(4) void align_pair_multi_kernel(const PairMultiParams M);
+WV_KERNEL_OCC(MANTA_PAIR_MULTI_OCC) void align_pair_multi_kernel(const PairMultiParams M);
 #else
-WV_KERNEL_OCC(4) void align_pair_multi_kernel(const PairMultiParams M)
+WV_KERNEL_OCC(MANTA_PAIR_MULTI_OCC) void align_pair_multi_kernel(const PairMultiParams M)
 {
   uint8_t* slab = M.A.ptr_ws + uint64_t(wv::block()) * M.A.ptr_ws_stride;
   unsigned n0 = 0, n1 = 0, n2 = 0, n3 = 0, n4 = 0, n5 = 0;  // tasks per queue position
@@ -353,7 +391,7 @@ WV_KERNEL_OCC(4) void align_pair_multi_kernel(const PairMultiParams M)
     const unsigned  ta = ids[ia], tb = ids[ib];
     {
       // The queue hands out the long sweeps first, but a short contig against a whole reference window is one dependent chain of
-      // E x (G + 63) steps' worth of work -- longer than the AVERAGE load of a wave in a block of ~2 pairs per wave -- and under
+      // E x (G + 50..63) steps' worth of work -- longer than the AVERAGE load of a wave in a block of ~2 pairs per wave -- and under
       // an even share of a saturated SIMD it would finish last with the device idling around it.  Long pairs therefore issue
       // ahead of the short ones of their SIMD; the short ones fill the gaps.
       const unsigned ga = M.A.tasks[ta].ref1_len, gb = M.A.tasks[tb].ref1_len;

@@ -651,7 +651,7 @@ int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates)
     // so a grid that is off costs time, never results) and its slabs from what the host knows (longest reference window,
     // longest possible contig).  The counts come back with the results.
     uint32_t hSmall[40];
-    const int    maxWaves = std::max(1, ctx->cuCount * alignWavesPerCu());
+    const int    maxWaves = std::max(1, ctx->cuCount * smallsvAlignWavesPerCu());
     const size_t wsBudget = workspaceBudget(size_t(48) << 30);
     bool         fromHistory = b->bucketHistory && b->stageBehindRun && !std::getenv("MANTA_AMD_SYNC_BUCKETS");  // (no host wait)
     struct Launch {

@@ -257,6 +257,13 @@ inline int alignWavesPerCu()
   return std::getenv("MANTA_AMD_ALIGN_WAVES_PER_CU") ? std::atoi(std::getenv("MANTA_AMD_ALIGN_WAVES_PER_CU")) : 16;
 }
 
+/// the small-SV pipeline's aligner launches: as many waves per CU (four SIMDs) as align_pair_multi_kernel is compiled to hold
+/// (align_pair.hpp: MANTA_PAIR_MULTI_OCC waves per SIMD; DESIGN 5.2 has the measurement behind the choice)
+inline int smallsvAlignWavesPerCu()
+{
+  return std::getenv("MANTA_AMD_ALIGN_WAVES_PER_CU") ? std::atoi(std::getenv("MANTA_AMD_ALIGN_WAVES_PER_CU")) : 4 * MANTA_PAIR_MULTI_OCC;
+}
+
 /// bucket_count() transitions of the libstdc++ this library is linked against, recorded from a live
 /// std::unordered_map (the reference's repeat search iterates such maps: assembly/IterativeAssembler.cpp:630-641)
 inline void recordGrowthSchedule(std::vector<uint32_t>& sizes, std::vector<uint32_t>& buckets, const uint32_t upTo)

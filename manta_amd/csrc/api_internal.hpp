@@ -558,8 +558,7 @@ struct AsmStage {
           if (manta_dev::lgPileFits(re - rb, maxAsm, w, mw, longest)) {  // (the test LdsGraph::pack() makes on the device)
             p.ldsFit++;
             cost[l] |= uint64_t(1) << 63;  // (marks the locus for the split below; reads x bases stays far below 2^62)
-          } else if ((re - rb) + 2 * maxAsm <= manta_dev::LGL_MAX_READS && w + 2 <= manta_dev::LGL_MAX_PILE + 2 &&
-                     (!read_off || b + 64 <= manta_dev::LGL_STAGE_BYTES)) {
+          } else if (manta_dev::lglPileFits(re - rb, maxAsm, w, mw, longest, b, read_off != nullptr)) {  // (... LdsGraphL::pack() makes)
             p.ldsFitBig++;
             cost[l] |= uint64_t(1) << 62;  // the pipeline's big class
           }

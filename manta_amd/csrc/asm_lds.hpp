@@ -6,7 +6,8 @@
 //                  word IS its identity: claim + one ds_or into the slot's read set) -> counts -> SORT of the words into the
 //                  reference's seed order (:686-696: count descending, k-mer ascending) -> 8-byte node records with successor /
 //                  predecessor links in that numbering -> proof of acyclicity from the reads' offsets -> the compact graph (8 bytes
-//                  per word + 16 per word with more than one read) goes to a per-locus slab in global memory.
+//                  per word + 16 per word with more than one read) goes to a per-locus slab in global memory.  (LdsGraph below; what it
+//                  shares with the big class' graph_big_kernel, asm_lds_big.hpp, is LdsGraphBase: asm_lds_base.hpp.)
 //   contig_kernel  (asm_contig.hpp) one single-wave workgroup per locus, only the compact graph in LDS (12-19 KB for a config-2
 //                  locus: eight per CU): cycle test where there is no proof, the contig loop (:685-713) on speculative lane-per-seed
 //                  walks (:149-501), selectContigs (:722-842), output.
@@ -221,6 +222,8 @@ struct LgS {
   static const unsigned UNUSED_DW = 64;  ///< dwords of the "unusedWords" bitmap
   static const unsigned CNT_SH = 44, FIRST_SH = 55, LAST_SH = 57, SELF_SH = 59, SOVF_SH = 60, POVF_SH = 61;
 };
+/// the only read of a single-read word: a field only the small class' record has (the big class: LgSlab::rd1)
+WV_DEV unsigned lg8Read(const FRec8 w) { return unsigned(w >> 48) & 0x7fu; }
 struct LgL {
   static const bool     BIG       = true;
   static const unsigned ID_BITS   = 13;
@@ -420,45 +423,19 @@ inline unsigned long long* fastStats()
 #define LG_STAT(i, n) do { } while (0)
 #endif
 
-// record fields
-WV_DEV unsigned lg8Succ(const FRec8 w, const unsigned i) { return unsigned(w >> (11 * i)) & 0x7ffu; }         // id + 1
-WV_DEV unsigned lg8Pred(const FRec8 w, const unsigned i) { return unsigned(w >> (22 + 11 * i)) & 0x7ffu; }    // id + 1
-WV_DEV unsigned lg8Cnt(const FRec8 w) { return unsigned(w >> 44) & 15u; }
-WV_DEV unsigned lg8Read(const FRec8 w) { return unsigned(w >> 48) & 0x7fu; }
-WV_DEV unsigned lg8FirstBase(const FRec8 w) { return unsigned(w >> 55) & 3u; }
-WV_DEV unsigned lg8LastBase(const FRec8 w) { return unsigned(w >> 57) & 3u; }
-WV_DEV bool     lg8SelfLoop(const FRec8 w) { return (w >> 59) & 1u; }
-WV_DEV bool     lg8SOvf(const FRec8 w) { return (w >> 60) & 1u; }
-WV_DEV bool     lg8POvf(const FRec8 w) { return (w >> 61) & 1u; }
-static const uint64_t LG_M22 = (uint64_t(1) << 22) - 1;
-static const uint64_t LG_M44 = (uint64_t(1) << 44) - 1;
-/// the (up to four) neighbours of word `nd` as 4 x 11 bits: the two of the record, the rest from the overflow table `ovf`
-/// (u16 {word, third, fourth, -}, `nOvf` entries; searched only for the flagged words)
-WV_DEV uint64_t lg8Links(const FRec8 w, const unsigned nd, const bool succ, const uint16_t* ovf, const unsigned nOvf)
-{
-  uint64_t l = (succ ? w : (w >> 22)) & LG_M22;
-  if (succ ? lg8SOvf(w) : lg8POvf(w)) {
-    for (unsigned e = 0; e < nOvf; ++e)
-      if (unsigned(ovf[4 * e]) == nd) l |= (uint64_t(ovf[4 * e + 1]) << 22) | (uint64_t(ovf[4 * e + 2]) << 33);
-  }
-  return l;
-}
-WV_DEV unsigned lgLinkId(const uint64_t w, const unsigned c)
-{
-  const unsigned f = unsigned(w >> (11 * c)) & 0x7ffu;
-  return f ? f - 1 : ASM_NONE;
-}
+}  // namespace manta_dev
+
+#include "asm_lds_base.hpp"  // LdsGraphBase: what graph_kernel and graph_big_kernel share
+
+namespace manta_dev {
 
 // ====================================================================================================================
 // graph_kernel
 // ====================================================================================================================
-struct LdsGraph {
-  const AsmParams& P;
-  const LgParams&  G;
-  char*            lds;
-  unsigned         tw, tn, lane;
-  uint32_t *       hdr, *rd, *dbase, *whist, *slots, *keyArr, *codes, *nmask;
-  uint16_t *       rdm, *sortA, *sortB, *slotId;
+struct LdsGraph : LdsGraphBase<LgGraphS> {
+  typedef LgRec<LgS> R;
+  uint32_t *       slots, *keyArr;
+  uint16_t *       sortA, *sortB, *slotId;
   uint8_t*         cntArr;
   FSet*            sets;
   FRec8*           nodes;   // records (the sets' bytes, after the bitsets have left for the slab)
@@ -466,19 +443,9 @@ struct LdsGraph {
   int16_t*         phi;     // potential of a word (id): offset of its first read + position in it
   int16_t*         roff;    // offset of a read (overlays rdm after the table pass)
   uint32_t*        filter;  // presence filter (maybePresent)
-  unsigned         nNormal, W, k, nNodes, nFat, nEligible, lowTier, codeWords;
-  uint64_t         tMark;
 
-  WV_DEV LdsGraph(const AsmParams& p, const LgParams& g, char* base) : P(p), G(g), lds(base)
+  WV_DEV LdsGraph(const AsmParams& p, const LgParams& g, char* base) : LdsGraphBase<LgGraphS>(p, g, base)
   {
-    tw     = unsigned(wv::wave_in_wg());
-    tn     = unsigned(wv::wg_waves());
-    lane   = unsigned(wv::lane());
-    hdr    = reinterpret_cast<uint32_t*>(lds + LG_OFF_HDR);
-    rd     = reinterpret_cast<uint32_t*>(lds + LG_OFF_RD);
-    rdm    = reinterpret_cast<uint16_t*>(lds + LG_OFF_RDM);
-    dbase  = reinterpret_cast<uint32_t*>(lds + LG_OFF_DBASE);
-    whist  = reinterpret_cast<uint32_t*>(lds + LG_OFF_WHIST);
     slots  = reinterpret_cast<uint32_t*>(lds + LG_OFF_SLOTS);
     sets   = reinterpret_cast<FSet*>(lds + LG_OFF_SETS);
     nodes  = reinterpret_cast<FRec8*>(lds + LG_OFF_SETS);
@@ -491,124 +458,6 @@ struct LdsGraph {
     keyArr = reinterpret_cast<uint32_t*>(lds + LG_OFF_KEYS);
     slotId = reinterpret_cast<uint16_t*>(lds + LG_OFF_KEYS);
     cntArr = reinterpret_cast<uint8_t*>(lds + LG_OFF_CNT);
-    codes  = reinterpret_cast<uint32_t*>(lds + LG_OFF_DYN);
-    nmask  = codes;
-  }
-
-  /// per-phase shader clocks of the workgroup's first wave (-DMANTA_ASM_PROFILE).  -DMANTA_LG_PROFILE_GRAPH: the eight counters
-  /// split graph_kernel alone (`fine`: 0 pack, 1 table, 2 successor links, 3 counts + radix passes, 4 ties + ids, 5 slab + bitsets +
-  /// record init, 6 predecessors + siblings, 7 speculation list + slab write); contig_kernel counts nothing then
-  WV_DEV void tick(const int phase, const int fine)
-  {
-#ifdef MANTA_ASM_PROFILE
-    const uint64_t now = wv::clock();
-#ifdef MANTA_LG_PROFILE_GRAPH
-    const int slot = fine;
-#else
-    const int slot = phase;
-#endif
-    if (P.phase_cycles && tw == 0 && lane == 0) wv::atomic_add(&P.phase_cycles[slot], (unsigned long long)(now - tMark));
-    tMark = now;
-#else
-    (void)phase;
-    (void)fine;
-#endif
-  }
-
-  /// every wave of the workgroup has written what the others read next
-  WV_DEV void teamSync() const
-  {
-    wv::sync();
-    wv::wg_barrier();
-  }
-  WV_DEV unsigned tid() const { return 64 * tw + lane; }
-  WV_DEV unsigned nThreads() const { return 64 * tn; }
-
-  // ---- keys (2-bit codes, 16 bases per dword, MSB first: dword order == base order) ----
-  template <int KW>
-  WV_DEV Key<KW> keyAt(const unsigned pb) const
-  {
-    Key<KW>        key;
-    const unsigned kw = (k + 15) >> 4;
-    const unsigned wi = pb >> 4, sh = (pb & 15) * 2;
-    uint32_t       raw[KW + 1];
-    for (int i = 0; i <= KW; ++i) raw[i] = (unsigned(i) <= kw) ? codes[wi + i] : 0u;
-    for (int i = 0; i < KW; ++i) {
-      uint32_t v = 0;
-      if (unsigned(i) < kw) {
-        v                   = uint32_t((((uint64_t(raw[i]) << 32) | raw[i + 1]) << sh) >> 32);
-        const unsigned have = k - 16u * unsigned(i);
-        if (have < 16) v &= ~((1u << (32 - 2 * have)) - 1u);
-      }
-      key.w[i] = v;
-    }
-    return key;
-  }
-  template <int KW>
-  WV_DEV static bool keyEq(const Key<KW>& a, const Key<KW>& b)
-  {
-    bool eq = true;
-    for (int i = 0; i < KW; ++i) eq = eq && (a.w[i] == b.w[i]);
-    return eq;
-  }
-  template <int KW>
-  WV_DEV static bool keyLess(const Key<KW>& a, const Key<KW>& b)
-  {
-    for (int i = 0; i < KW; ++i)
-      if (a.w[i] != b.w[i]) return a.w[i] < b.w[i];
-    return false;
-  }
-  template <int KW>
-  WV_DEV void keySetBase(Key<KW>& key, const unsigned i, const unsigned c) const
-  {
-    const unsigned sh = 30 - 2 * (i & 15);
-    for (int w = 0; w < KW; ++w)
-      if (unsigned(w) == (i >> 4)) key.w[w] = (key.w[w] & ~(3u << sh)) | (c << sh);
-  }
-  /// word[1..k-1] + c
-  template <int KW>
-  WV_DEV Key<KW> keyShiftAppend(const Key<KW>& key, const unsigned c) const
-  {
-    Key<KW> r;
-    for (int w = 0; w < KW; ++w) r.w[w] = (key.w[w] << 2) | ((w + 1 < KW) ? (key.w[w + 1] >> 30) : 0u);
-    keySetBase(r, k - 1, c);
-    return r;
-  }
-  /// hash of a key: bucket from the low bits, 17-bit tag from the high bits
-  template <int KW>
-  WV_DEV uint32_t keyHash(const Key<KW>& key) const
-  {
-    const unsigned kw = (k + 15) >> 4;
-    uint32_t       h  = 0x811C9DC5u;
-    for (int i = 0; i < KW; ++i)
-      if (unsigned(i) < kw) h = hashMix(h, key.w[i]);
-    h ^= h >> 13;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 16;
-    return h;
-  }
-  WV_DEV uint32_t prefix32(const unsigned pb) const  // the word's first 16 bases (fewer: zero padded)
-  {
-    const unsigned wi = pb >> 4, sh = (pb & 15) * 2;
-    uint32_t       v  = codes[wi];
-    if (sh) v = (v << sh) | (codes[wi + 1] >> (32 - sh));
-    if (k < 16) v &= ~((1u << (32 - 2 * k)) - 1u);
-    return v;
-  }
-
-  WV_DEV bool windowHasN(const unsigned maskWordBase, const unsigned j) const
-  {
-    unsigned pos = j, left = k;
-    while (left > 0) {
-      const unsigned wi = pos >> 5, bit = pos & 31;
-      const unsigned take = (32 - bit < left) ? (32 - bit) : left;
-      uint32_t       m    = nmask[maskWordBase + wi] >> bit;
-      if (take < 32) m &= (1u << take) - 1u;
-      if (m) return true;
-      pos += take;
-      left -= take;
-    }
-    return false;
   }
 
   /// slot of `key` or ASM_NONE.  One 16-byte read per probed bucket; an empty slot ends the search (the slots of a bucket fill
@@ -659,143 +508,16 @@ struct LdsGraph {
     teamSync();
   }
 
-  WV_DEV uint64_t plShift(const unsigned locus, const unsigned i) const
-  {
-    return P.pl_chunk_shift ? P.pl_chunk_shift[3 * size_t(locus / P.chunk_loci) + i] : uint64_t(0);
-  }
-
   // ------------------------------------------------------------------------------------------------
-  // stage 0: the locus' reads -> 2 bit + N bitmap in LDS, from any of the three input forms (1 byte per base, the same
-  // arriving chunk by chunk behind the running kernel, packed piles).  False: the locus does not fit this path.
-  // (every wave computes the same offsets; the reads are dealt out eight at a time)
+  // stage 0: the locus' reads -> 2 bit + N bitmap in LDS (LdsGraphBase: scanPile, fillPile).  False: the locus does not fit this path.
   // ------------------------------------------------------------------------------------------------
   WV_DEV bool pack(const unsigned locus)
   {
-    const unsigned rBegin = P.locus_read_begin[locus], rEnd = P.locus_read_begin[locus + 1];
-    nNormal               = rEnd - rBegin;
-    if (!lgPileFits(nNormal, P.opt.maxAssemblyCount, 0, 0, 0)) return false;  // (the read count, before the descriptors are written)
-    W = (nNormal + 2 * P.opt.maxAssemblyCount + 63) / 64;
-    if (W == 0) W = 1;
-    const uint64_t plR = plShift(locus, 0), plC = plShift(locus, 1), plM = plShift(locus, 2);
-    unsigned       cw = 0, mw = 0, nb = 0;  // code dwords, N-bitmap dwords, bases so far
-    uint16_t*      rstart  = reinterpret_cast<uint16_t*>(hdr + 64);
-    bool           tooLong = false;
-    for (unsigned base = 0; base < nNormal; base += 64) {
-      const unsigned r   = base + lane;
-      unsigned       len = 0;
-      if (r < nNormal) len = P.pl_codes ? P.pl_read_len[rBegin + r + plR] : unsigned(P.read_off[rBegin + r + 1] - P.read_off[rBegin + r]);
-      if (len > 0xffffu) tooLong = true;
-      const unsigned myC = (r < nNormal) ? (len + 15) / 16 + 1 : 0u;  // +1 padding dword so key fetches may read one past
-      const unsigned myM = (r < nNormal) ? (len + 31) / 32 + 1 : 0u;
-      unsigned       sc = myC, sm = myM, sb = (r < nNormal) ? len : 0u;
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned oc = wv::shfl(sc, wv::lane() - off), om = wv::shfl(sm, wv::lane() - off), ob = wv::shfl(sb, wv::lane() - off);
-        if (wv::lane() >= off) {
-          sc += oc;
-          sm += om;
-          sb += ob;
-        }
-      }
-      const unsigned cwo = cw + sc - myC, mwo = mw + sm - myM;
-      if (tw == 0 && r < nNormal && cwo <= 0x7ffu) {
-        rd[r]     = cwo | ((len & 0xffffu) << 11);
-        rdm[r]    = uint16_t(mwo);
-        rstart[r] = uint16_t(nb + sb - len);
-      }
-      cw += wv::readlane(sc, 63);
-      mw += wv::readlane(sm, 63);
-      nb += wv::readlane(sb, 63);
-    }
-    if (!lgPileFits(nNormal, P.opt.maxAssemblyCount, cw, mw, wv::any(tooLong) ? 0x10000u : 0u)) return false;
-    const unsigned cwPad = (cw + 2 + 3) & ~3u, mwPad = (mw + 2 + 3) & ~3u;
-    codeWords = cw + 2;
-    nmask     = codes + cwPad;
-    for (unsigned i = tid(); i < mw + 2; i += nThreads()) nmask[i] = 0;
-    if (tid() == 0) hdr[LG_H_FLAG] = 0;
-    teamSync();
-    if (P.pl_codes) {  // packed piles arrive in this layout: copy, 8 lanes per read
-      for (unsigned base = 8 * tw; base < nNormal; base += 8 * tn) {
-        const unsigned r = base + (lane >> 3);
-        if (r >= nNormal) continue;
-        const unsigned  d = rd[r], cwo = d & 0x7ffu, len = (d >> 11) & 0xffffu, mwo = rdm[r];
-        const unsigned  nCw = (len + 15) / 16, nMw = (len + 31) / 32;
-        const uint32_t* sc  = P.pl_codes + (P.pl_code_off[rBegin + r + plR] + plC);
-        const uint32_t* sm  = P.pl_nmask + (P.pl_mask_off[rBegin + r + plR] + plM);
-        for (unsigned wi = (lane & 7); wi <= nCw; wi += 8) codes[cwo + wi] = (wi < nCw) ? sc[wi] : 0u;
-        bool sawN = false;
-        for (unsigned wi = (lane & 7); wi < nMw; wi += 8) {
-          const uint32_t m = sm[wi];
-          nmask[mwo + wi]  = m;
-          sawN             = sawN || (m != 0);
-        }
-        if (sawN) wv::atomic_or(&rd[r], 1u << 27);
-      }
-      if (tid() < 2) codes[cw + tid()] = 0;
-      teamSync();
-      return true;
-    }
-    bool           bad   = false;
-    const uint32_t shift = P.chunk_shift ? P.chunk_shift[locus / P.chunk_loci] : 0u;
-    // The locus' bases are one contiguous run of the input arena: every thread fetches 16-byte pieces of it into LDS (the sets'
-    // bytes, unused until the table pass) -- all loads in flight at once, one memory latency for the whole pile -- and the
-    // conversion below reads its bytes from there.
-    char* const stage = lds + LG_OFF_SETS;
-    unsigned    lead  = 0;
-    {
-      const uintptr_t g0 = reinterpret_cast<uintptr_t>(P.bases + P.read_off[rBegin] + shift);
-      lead               = unsigned(g0 & 15);
-      const u32x4*   gsrc    = reinterpret_cast<const u32x4*>(g0 - lead);
-      const unsigned nChunks = (lead + nb + 15) / 16 + 1;  // (+1: the byte funnel reads up to four bytes past a read's last dword; the arena is padded)
-      for (unsigned c = tid(); c < nChunks; c += nThreads()) reinterpret_cast<u32x4*>(stage)[c] = gsrc[c];
-    }
-    teamSync();
-    // 8 lanes per read, 8 reads per pass: lane (g, i) converts code dwords i, i+8, ... of read (base + g)
-    for (unsigned base = 8 * tw; base < nNormal; base += 8 * tn) {
-      const unsigned r = base + (lane >> 3);
-      if (r >= nNormal) continue;
-      const char*    src = stage + lead + rstart[r];
-      const unsigned d = rd[r], cwo = d & 0x7ffu, len = (d >> 11) & 0xffffu, mwo = rdm[r];
-      const unsigned nCw = (len + 15) / 16 + 1;
-      bool           sawN = false;
-      for (unsigned wi = (lane & 7); wi < nCw; wi += 8) {
-        uint32_t code = 0, nbits = 0;
-        if (wi * 16 < len) {
-          // 16 bases = five aligned dword reads + a byte funnel
-          const uintptr_t addr = reinterpret_cast<uintptr_t>(src + wi * 16);
-          const uint32_t* ap   = reinterpret_cast<const uint32_t*>(addr & ~uintptr_t(3));
-          const unsigned  sh   = unsigned(addr & 3) * 8;
-          uint32_t        dw[5];
-          for (int q = 0; q < 5; ++q) dw[q] = ap[q];
-          for (unsigned q = 0; q < 4; ++q) {
-            const uint32_t four = sh ? ((dw[q] >> sh) | (dw[q + 1] << (32 - sh))) : dw[q];
-            for (unsigned b4 = 0; b4 < 4; ++b4) {
-              const unsigned b = q * 4 + b4;
-              const unsigned i = wi * 16 + b;
-              unsigned       c = 0;
-              if (i < len) {
-                c = baseCode(uint8_t(four >> (8 * b4)));
-                if (c == 5) bad = true;
-                if (c >= 4) {
-                  nbits |= (1u << b);
-                  c = 0;
-                }
-              }
-              code |= c << (30 - 2 * b);
-            }
-          }
-        }
-        codes[cwo + wi] = code;
-        if (nbits) {
-          wv::atomic_or(&nmask[mwo + (wi >> 1)], (wi & 1) ? (nbits << 16) : nbits);
-          sawN = true;
-        }
-      }
-      if (sawN) wv::atomic_or(&rd[r], 1u << 27);
-    }
-    if (tid() < 2) codes[cw + tid()] = 0;
-    if (wv::any(bad) && lane == 0) wv::atomic_or(&hdr[LG_H_FLAG], 1u);  // bytes outside {A,C,G,T,N}: the general path decides what is exact
-    teamSync();
-    return wv::atomic_load(&hdr[LG_H_FLAG]) == 0;
+    Pile s;
+    if (!scanPile(locus, s)) return false;
+    if (!lgPileFits(nNormal, P.opt.maxAssemblyCount, s.cw, s.mw, s.tooLong ? 0x10000u : 0u)) return false;
+    nReads = nNormal;
+    return fillPile(locus, s);
   }
 
   // ------------------------------------------------------------------------------------------------
@@ -970,49 +692,13 @@ struct LdsGraph {
         if (i < c1) wv::atomic_add(&myHist[digitOf(src[i])], 1u);
       }
       teamSync();
-      // per digit: running offsets over the waves, totals; then the digit bases (four quarters of 64 digits, dealt out to the waves)
-      for (unsigned q = tw; q < 4; q += tn) {
-        const unsigned d   = 64 * q + lane;
-        unsigned       run = 0;
-        for (unsigned w = 0; w < tn; ++w) {
-          const unsigned c   = whist[256 * w + d];
-          whist[256 * w + d] = run;
-          run += c;
-        }
-        unsigned inc = run;
-        for (int off = 1; off < 64; off <<= 1) {
-          const unsigned o = wv::shfl(inc, int(lane) - off);
-          if (int(lane) >= off) inc += o;
-        }
-        dbase[d] = inc - run;  // exclusive inside the quarter
-        if (lane == 63) hdr[LG_H_TOT + q] = inc;
-      }
-      teamSync();
-      for (unsigned q = tw; q < 4; q += tn) {
-        unsigned before = 0;
-        for (unsigned p = 0; p < q; ++p) before += hdr[LG_H_TOT + p];
-        dbase[64 * q + lane] += before;
-      }
-      teamSync();
+      radixDigitBases(whist);
       for (unsigned i0 = c0; i0 < c1; i0 += 64) {
         const unsigned i     = i0 + lane;
         const bool     valid = i < c1;
         const unsigned slot  = valid ? unsigned(src[i]) : 0u;
         const unsigned d     = valid ? digitOf(slot) : 0u;
-        uint64_t       peers = wv::ballot(valid);
-        for (int bit = 0; bit < 8; ++bit) {
-          const bool     on = (d >> bit) & 1u;
-          const uint64_t m  = wv::ballot(valid && on);
-          peers &= on ? m : ~m;
-        }
-        unsigned base = 0;
-        if (valid) base = dbase[d] + myHist[d];
-        wv::sync();
-        if (valid) {
-          dst[base + unsigned(wv::popc(peers & ((uint64_t(1) << lane) - 1)))] = uint16_t(slot);
-          if ((peers >> lane) == 1u) myHist[d] += unsigned(wv::popc(peers));  // the highest lane of the digit's group
-        }
-        wv::sync();
+        radixScatter(valid, slot, d, dst, myHist);
       }
       teamSync();
       if (pass == 2 && tid() == 0) {
@@ -1073,102 +759,21 @@ struct LdsGraph {
   // checked edge by edge in the links pass, so a wrong or inconsistent offset (indel haplotypes, an anchor cycle between reads
   // inserted at the same time) costs nothing but the proof: contig_kernel then runs its peel.
   // ------------------------------------------------------------------------------------------------
-  /// read that owns packed base index pb (the reads' code offsets ascend)
-  WV_DEV unsigned readOfPb(const unsigned pb) const
-  {
-    const unsigned cwd = pb >> 4;
-    unsigned       lo = 0, hi = nNormal;  // rd[lo].cwo <= cwd < rd[hi].cwo
-    while (hi - lo > 1) {
-      const unsigned mid = (lo + hi) >> 1;
-      if ((rd[mid] & 0x7ffu) <= cwd) lo = mid; else hi = mid;
-    }
-    return lo;
-  }
   template <int KW>
   WV_DEV void readOffsets()
   {
     if (tw == 0) {
-      const uint32_t* anch = reinterpret_cast<const uint32_t*>(lds + LG_OFF_ANCH);
-      int32_t*        off  = reinterpret_cast<int32_t*>(lds + LG_OFF_ANCH) + LG_MAX_READS;
-      uint8_t*        par  = reinterpret_cast<uint8_t*>(hdr + LG_H_PAR);
-      int32_t         myOff[2];
-      unsigned        myPar[2], myRoot[2];
-      for (unsigned h = 0; h < 2; ++h) {
-        const unsigned r = lane + 64 * h;
-        myOff[h] = 0;
-        myPar[h] = r;
-        myRoot[h] = r;
-        if (r < nNormal) {
-          const uint32_t a = anch[r];
-          if (a != LG_NO_ANCHOR) {
-            const unsigned apb = a & 0x7fffu, j = a >> 15;
-            const unsigned r0  = readOfPb(apb);
-            myPar[h] = r0;
-            myOff[h] = int32_t(apb - 16u * (rd[r0] & 0x7ffu)) - int32_t(j);
-          }
-        }
-      }
-      wv::sync();  // (every anchor has been read: the offsets take the second half of the same array... and rdm's bytes below)
-      for (unsigned h = 0; h < 2; ++h) {
-        off[lane + 64 * h] = myOff[h];
-        par[lane + 64 * h] = uint8_t(myPar[h]);
-      }
-      wv::sync();
-      for (int round = 0; round < 7; ++round) {
-        int32_t  po[2];
-        unsigned pp[2];
-        for (unsigned h = 0; h < 2; ++h) {
-          po[h] = off[myPar[h]];
-          pp[h] = par[myPar[h]];
-        }
-        wv::sync();
-        for (unsigned h = 0; h < 2; ++h) {
-          const unsigned r = lane + 64 * h;
-          if (myPar[h] != r) {  // (a root keeps its offset)
-            myOff[h] += po[h];
-            if (pp[h] == myPar[h]) {  // the parent is a root: done after this addition
-              off[r] = myOff[h];
-              par[r] = uint8_t(r);
-              myRoot[h] = myPar[h];
-              myPar[h] = r;
-            } else {
-              off[r]   = myOff[h];
-              par[r]   = uint8_t(pp[h]);
-              myPar[h] = pp[h];
-            }
-          }
-        }
-        wv::sync();
-      }
-#ifdef MANTA_WAVE_EMU
-      if (std::getenv("MANTA_EMU_PROOF_TRACE"))
-        for (unsigned h = 0; h < 2; ++h)
-          if (lane + 64 * h < nNormal) std::fprintf(stderr, "  read %u: anchor %08x off %d par %u\n", lane + 64 * h, anch[lane + 64 * h], myOff[h], myPar[h]);
-#endif
-      // (myRoot is the read a read's offset was completed through: the root for the root's children, a finished inner read for the reads
-      // below it.  The roots proper by pointer jumping -- the trees below are told apart by them)
-      {
-        uint8_t* rootTmp = reinterpret_cast<uint8_t*>(lds + LG_OFF_WHIST);  // (the histograms are not in use before the sort)
-        for (unsigned h = 0; h < 2; ++h) rootTmp[lane + 64 * h] = uint8_t(myRoot[h]);
-        wv::sync();
-        for (int round = 0; round < 7; ++round) {
-          unsigned up[2];
-          for (unsigned h = 0; h < 2; ++h) up[h] = rootTmp[rootTmp[lane + 64 * h]];
-          wv::sync();
-          for (unsigned h = 0; h < 2; ++h) rootTmp[lane + 64 * h] = uint8_t(up[h]);
-          wv::sync();
-        }
-        for (unsigned h = 0; h < 2; ++h) myRoot[h] = rootTmp[lane + 64 * h];
-      }
+      int32_t  myOff[RPL];
+      unsigned myRoot[RPL];
+      anchorForest(myOff, myRoot);
+      int32_t* off = readOff();
       // ---- second chance.  A read whose words were all new when it went in -- the reads of a step are inserted by eight waves at
       // once, so which of two overlapping reads "was first" is a race -- has no anchor and is the root of a tree of its own, at
       // offset 0: one such tree beside the main one and the proof is lost.  Now that every word is in the table, such a root
       // looks its words up again and ties itself (and its tree) to the first word that a read of the MAIN tree brought.  Any
       // function phi proves acyclicity if it rises by one along every edge, so nothing here can make the proof unsound.
       if (!(G.flags & LG_FLAG_NO_RESCUE)) {
-        uint8_t* rootOf = reinterpret_cast<uint8_t*>(lds + LG_OFF_WHIST);  // (the histograms are not in use before the sort)
-        for (unsigned h = 0; h < 2; ++h) rootOf[lane + 64 * h] = uint8_t(myRoot[h]);
-        wv::sync();
+        uint8_t* rootOf = rootOfRead();
         // the main tree: the root with the most reads
         unsigned mainRoot = 0, mainSize = 0;
         for (unsigned h = 0; h < 2; ++h) {
@@ -1383,7 +988,7 @@ struct LdsGraph {
       if (m == 0) {
         const unsigned pb  = slots[sortA[nd]] & 0x7fffu;
         const Key<KW>  key = keyAt<KW>(pb);
-        const unsigned lastBase = lg8LastBase(w);
+        const unsigned lastBase = R::lastBase(w);
         unsigned       found[3] = {LG_NO_SLOT, LG_NO_SLOT, LG_NO_SLOT};
         unsigned       nf = 0;
         for (unsigned c = 0; c < 4; ++c) {
@@ -1427,9 +1032,9 @@ struct LdsGraph {
     // a word's only successor / number of predecessors, self loops aside (a word with an overflow entry has three or more)
     auto outOnly = [&](const FRec8 w, const unsigned nd, unsigned& od) -> unsigned {
       unsigned only = ASM_NONE;
-      od            = lg8SOvf(w) ? 3u : 0u;
+      od            = R::sOvf(w) ? 3u : 0u;
       for (unsigned c = 0; c < 2; ++c) {
-        const unsigned f = lg8Succ(w, c);
+        const unsigned f = R::succ(w, c);
         if (f && f - 1 != nd) {
           od++;
           only = f - 1;
@@ -1438,9 +1043,9 @@ struct LdsGraph {
       return only;
     };
     auto inDeg = [&](const FRec8 w, const unsigned nd) -> unsigned {
-      unsigned id = lg8POvf(w) ? 3u : 0u;
+      unsigned id = R::pOvf(w) ? 3u : 0u;
       for (unsigned c = 0; c < 2; ++c) {
-        const unsigned f = lg8Pred(w, c);
+        const unsigned f = R::pred(w, c);
         if (f && f - 1 != nd) id++;
       }
       return id;
@@ -1534,36 +1139,8 @@ struct LdsGraph {
     if (cls == LG_CLASSES) return false;
     uint16_t*      gSpec = reinterpret_cast<uint16_t*>(slab + SL.spec);
     const unsigned nSpec = speculationList(gSpec);
-    // the rest of the slab
-    FRec8* gRec = reinterpret_cast<FRec8*>(slab + SL.recs);
-    for (unsigned i = tid(); i < nNodes; i += nThreads()) gRec[i] = nodes[i];
-    const unsigned nSib = wv::atomic_load(&hdr[LG_H_NSIB]), nSovf = wv::atomic_load(&hdr[LG_H_NSOVF]), nPovf = wv::atomic_load(&hdr[LG_H_NPOVF]);
-    {
-      // the three side tables lie back to back in LDS and in the slab (fixed capacities)
-      const uint16_t* tsrc = reinterpret_cast<const uint16_t*>(lds + LG_OFF_SIB);
-      uint16_t*       tdst = reinterpret_cast<uint16_t*>(slab + SL.sib);
-      for (unsigned i = tid(); i < 4 * (LG_SIB_CAP + 2 * LG_OVF_CAP); i += nThreads()) tdst[i] = tsrc[i];
-    }
-    uint32_t* gCodes = reinterpret_cast<uint32_t*>(slab + SL.codes);
-    for (unsigned i = tid(); i < codeWords; i += nThreads()) gCodes[i] = codes[i];
+    writeSlab(locus, off, SL, nodes, nSpec, need, acyclic, 0, 0);
     if (tid() == 0) {
-      LgHdr h;
-      h.nNodes    = nNodes;
-      h.nFat      = nFat;
-      h.k         = k;
-      h.nNormal   = nNormal;
-      h.nEligible = nEligible;
-      h.nSpec     = nSpec;
-      h.nSib      = nSib;
-      h.codeWords = codeWords;
-      h.W         = W;
-      h.need      = need;
-      h.nSovf     = nSovf;
-      h.nPovf     = nPovf;
-      h.acyclic   = acyclic ? 1u : 0u;
-      h.nPseudo = h.cyclic = h.nCore = 0;
-      *reinterpret_cast<LgHdr*>(slab) = h;
-      G.slab_off[locus]               = off;
       const unsigned slot = wv::atomic_add(&G.class_count[cls], 1u);
       if (cls == 0 && G.cost_bins) {
         const unsigned b = (G.class_bytes[0] - need) / 1024u;
@@ -1607,29 +1184,7 @@ struct LdsGraph {
 template <int MAXKW>
 WV_KERNEL_WG(LG_WAVES) WV_WAVES_PER_SIMD(MANTA_LG_WAVES_PER_SIMD) void graph_kernel(const LgArgs A)
 {
-  const AsmParams& P = A.P;
-  const LgParams&  G = A.G;
-  char*          lds = wv::lds_single();
-  uint32_t*      hdr = reinterpret_cast<uint32_t*>(lds + LG_OFF_HDR);
-  const unsigned tw  = unsigned(wv::wave_in_wg());
-  while (true) {
-    if (tw == 0 && wv::lane() == 0) hdr[LG_H_SLOT] = wv::atomic_add(P.counter, 1u);
-    wv::sync();
-    wv::wg_barrier();
-    const unsigned slot = wv::first(wv::atomic_load(&hdr[LG_H_SLOT]));
-    if (slot >= P.n_loci) break;
-    const unsigned locus   = P.locus_ids ? P.locus_ids[slot] : slot;
-    const bool     arrived = !P.upload_chunks_done || asmWaitUploaded(P, locus);
-    bool           ok      = false;
-    if (arrived) {
-      LdsGraph g(P, G, lds);
-      ok = g.template run<MAXKW>(locus);
-    }
-    wv::sync();
-    if (tw == 0 && !ok && wv::lane() == 0) P.punt_ids[wv::atomic_add(P.punt_count, 1u)] = locus;
-    wv::sync();
-    wv::wg_barrier();  // (the slot word is rewritten next)
-  }
+  lgGraphLoop<LdsGraph, MAXKW>(A, A.P.n_loci);
 }
 
 #if MANTA_TU != MANTA_TU_ALL

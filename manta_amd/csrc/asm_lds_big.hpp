@@ -4,8 +4,9 @@
 // loop): pack -> table pass -> sort into seed order -> 8-byte records with links -> proof of acyclicity -> compact graph to the
 // locus' slab.  contig_big_kernel (asm_contig.hpp, the same template as contig_kernel) does the serial half.
 //
-// One workgroup of LGL_WAVES = 16 wavefronts owns a CU's whole LDS (160 KB).  What does not scale from the small class and is done
-// differently here:
+// One workgroup of LGL_WAVES = 16 wavefronts owns a CU's whole LDS (160 KB).  What is the same text in both classes but for bit widths and
+// places -- keys, pack, the reads' anchor forest, the radix pieces, the slab's tail -- is LdsGraphBase (asm_lds_base.hpp) over LgGraphL below.
+// What does not scale from the small class and is done differently here:
 //   * READ SETS.  A set per table slot (8 192 x 32 bytes) does not fit, and it is not needed: nine words in ten have one read.  A
 //     slot starts as a single-read word whose read is implied by its first occurrence; the first instance that comes from ANOTHER
 //     read allocates a 4-qword set from a pool (one LDS counter) and publishes its index inside the slot word with a compare-and-
@@ -55,39 +56,58 @@ enum {
   LGL_H_NSOVF = 16, LGL_H_NPOVF = 17, LGL_H_NSPEC = 18
 };
 
-struct LdsGraphL {
+/// graph_big_kernel's numbers for the bodies the two graph kernels share (asm_lds_base.hpp; LgGraphS is graph_kernel's)
+struct LgGraphL {
+  static const unsigned CWO_BITS    = 12;
+  static const unsigned ANCH_BITS   = 16;
+  static const unsigned MAX_READS   = LGL_MAX_READS;
+  static const unsigned JUMP_ROUNDS = 8;
+  static const unsigned OFF_HDR = LGL_OFF_HDR, OFF_RD = LGL_OFF_RD, OFF_RDM = LGL_OFF_RDM, OFF_DYN = LGL_OFF_DYN;
+  static const unsigned OFF_RST = LGL_OFF_RST, OFF_PAR = LGL_OFF_PAR;
+  static const unsigned OFF_STAGE = LGL_OFF_POOL;  ///< pool + slots: LGL_STAGE_BYTES
+  static const unsigned OFF_ANCH = LGL_OFF_ANCH, OFF_DBASE = LGL_OFF_DBASE, OFF_WHIST = LGL_OFF_WHIST;
+  static const unsigned OFF_SIB = LGL_OFF_SIB, SIDE_U16 = 4 * (LG_SIB_CAP + 2 * LGL_OVF_CAP);  ///< the three side tables, back to back
+  static const unsigned H_SLOT = LGL_H_SLOT, H_FLAG = LGL_H_FLAG, H_TOT = LGL_H_TOT, H_NSIB = LGL_H_NSIB, H_NSOVF = LGL_H_NSOVF, H_NPOVF = LGL_H_NPOVF;
+};
+
+/// room of the dynamic region for a pile of cw / mw code / N-bitmap dwords (lgPileFits' units): codes + N bitmap, and the counts by id
+/// (u8[LGL_MAX_NODES]) that take the N bitmap's place behind the codes after the table pass
+WV_HD bool lglDynFits(const uint64_t cw, const uint64_t mw)
+{
+  const uint64_t cwPad = (cw + 2 + 3) & ~uint64_t(3), mwPad = (mw + 2 + 3) & ~uint64_t(3);
+  return cwPad + mwPad <= LGL_DYN_DWORDS && 4 * cwPad + LGL_MAX_NODES + 16 <= 4 * LGL_DYN_DWORDS;
+}
+/// The size envelope of the big class for a locus' OWN reads, as lgPileFits is the small class': ONE function for LdsGraphL::pack() and for
+/// the host's planning pass (AsmStage::plan), so that the host marks for this class exactly what the device takes.  bases: the pile's bases,
+/// staged as bytes when the input is `unpacked` (one byte per base).  The pseudo reads of a later word length are the device's business
+/// alone (pack).  (From LGL_MAX_PILE follow longest < 2^16 and -- mw <= cw / 2 + nReads -- the room: only the first two lines and the
+/// staged bytes ever bind.)
+WV_HD bool lglPileFits(const uint64_t nReads, const uint64_t maxAssemblyCount, const uint64_t cw, const uint64_t mw, const uint64_t longest,
+                       const uint64_t bases, const bool unpacked)
+{
+  if (nReads + 2 * maxAssemblyCount > LGL_MAX_READS) return false;
+  if (longest > 0xffffu || cw + 2 > LGL_MAX_PILE + 2) return false;
+  if (!lglDynFits(cw, mw)) return false;
+  return !unpacked || bases + 64 <= LGL_STAGE_BYTES;
+}
+
+struct LdsGraphL : LdsGraphBase<LgGraphL> {
   typedef FSetT<LgL> Set;
   typedef LgRec<LgL> R;
-  static const unsigned RPL = LGL_MAX_READS / 64;  ///< reads per lane where one wave handles all reads
-  const AsmParams& P;
-  const LgParams&  G;
-  char*            lds;
-  unsigned         tw, tn, lane;
-  uint32_t *       hdr, *rd, *dbase, *whist, *slots, *codes, *nmask, *filter;
-  uint16_t *       rdm, *rstart, *sortA, *sortB, *idPb;
+  uint32_t *       slots, *filter;
+  uint16_t *       sortA, *sortB, *idPb;
   uint8_t *        cntArr, *cntId;
   Set*             pool;
   Set*             poolOvf;  ///< sets LGL_POOL_CAP .. of the table pass: device memory (nullptr: none)
   uint16_t *       lexBySlot, *lexById;  ///< the words' lexicographic ranks (device memory, rounds only): sortWords leaves them, lexOrder copies them
   FRec8*           nodes;
   int16_t *        phi, *roff;
-  unsigned         nNormal, W, k, nNodes, nFat, nEligible, lowTier, codeWords;
-  unsigned         nReads, nPseudo, pseudoPb0;  ///< later word lengths: the previous length's contigs as reads nNormal .. nReads - 1 (packed bases from pseudoPb0 on)
+  unsigned         nPseudo, pseudoPb0;  ///< later word lengths: the previous length's contigs as reads nNormal .. nReads - 1 (packed bases from pseudoPb0 on)
   const LgIter*    it;
-  uint64_t         tMark;
 
-  WV_DEV LdsGraphL(const AsmParams& p, const LgParams& g, char* base) : P(p), G(g), lds(base)
+  WV_DEV LdsGraphL(const AsmParams& p, const LgParams& g, char* base) : LdsGraphBase<LgGraphL>(p, g, base)
   {
-    tw     = unsigned(wv::wave_in_wg());
-    tn     = unsigned(wv::wg_waves());
-    lane   = unsigned(wv::lane());
-    hdr    = reinterpret_cast<uint32_t*>(lds + LGL_OFF_HDR);
-    rd     = reinterpret_cast<uint32_t*>(lds + LGL_OFF_RD);
-    rdm    = reinterpret_cast<uint16_t*>(lds + LGL_OFF_RDM);
     roff   = reinterpret_cast<int16_t*>(lds + LGL_OFF_RDM);
-    rstart = reinterpret_cast<uint16_t*>(lds + LGL_OFF_RST);
-    dbase  = reinterpret_cast<uint32_t*>(lds + LGL_OFF_DBASE);
-    whist  = reinterpret_cast<uint32_t*>(lds + LGL_OFF_WHIST);
     pool   = reinterpret_cast<Set*>(lds + LGL_OFF_POOL);
     poolOvf = g.gws ? reinterpret_cast<Set*>(g.gws + size_t(wv::block_single()) * LGL_GWS_BYTES) : nullptr;
     lexBySlot = g.gws ? reinterpret_cast<uint16_t*>(g.gws + size_t(wv::block_single()) * LGL_GWS_BYTES + LGL_GWS_SETS) : nullptr;
@@ -100,161 +120,18 @@ struct LdsGraphL {
     phi    = reinterpret_cast<int16_t*>(lds + LGL_OFF_SORTB);
     cntArr = reinterpret_cast<uint8_t*>(lds + LGL_OFF_CNT);
     filter = reinterpret_cast<uint32_t*>(lds + LGL_OFF_CNT);
-    codes  = reinterpret_cast<uint32_t*>(lds + LGL_OFF_DYN);
-    nmask  = codes;
     cntId  = nullptr;
     nReads = nPseudo = 0;
     pseudoPb0 = 0x10000u;
     it        = nullptr;
   }
 
-  /// per-phase shader clocks of the workgroup's first wave (-DMANTA_ASM_PROFILE; the slots of graph_kernel's coarse profile)
-  /// coarse: 0 pack, 1 table + offsets, 2 sort + records, 4 slab.  -DMANTA_LG_PROFILE_GRAPH: the eight counters split this kernel alone
-  /// (`fine`: 0 pack, 1 table, 2 reads' offsets, 3 sort, 4 sets to the slab + slot rewrite + filter, 5 links, 6 speculation list, 7 slab write)
-  WV_DEV void tick(const int phase, const int fine)
-  {
-#ifdef MANTA_ASM_PROFILE
-    const uint64_t now = wv::clock();
-#ifdef MANTA_LG_PROFILE_GRAPH
-    const int slot = fine;
-#else
-    const int slot = phase;
-#endif
-    if (P.phase_cycles && tw == 0 && lane == 0) wv::atomic_add(&P.phase_cycles[slot], (unsigned long long)(now - tMark));
-    tMark = now;
-#else
-    (void)phase;
-    (void)fine;
-#endif
-  }
   /// why a locus was handed back (G.stats[2..9], read by the host's debug line): 2 envelope / alphabet, 3 table or set pool full,
   /// 4 too many words / side tables / no contig class, 5 slab arena full, 6 repeat_big_kernel, 7 contig kernel (LDS / contig length),
   /// 8 pseudo arena full, 9 more word lengths than rounds
   WV_DEV void why(const unsigned code) const
   {
     if (G.stats && tid() == 0) wv::atomic_add(&G.stats[code], 1u);
-  }
-  WV_DEV void teamSync() const
-  {
-    wv::sync();
-    wv::wg_barrier();
-  }
-  WV_DEV unsigned tid() const { return 64 * tw + lane; }
-  WV_DEV unsigned nThreads() const { return 64 * tn; }
-
-  // ---- keys (2-bit codes, 16 bases per dword, MSB first: dword order == base order) ----
-  template <int KW>
-  WV_DEV Key<KW> keyAt(const unsigned pb) const
-  {
-    Key<KW>        key;
-    const unsigned kw = (k + 15) >> 4;
-    const unsigned wi = pb >> 4, sh = (pb & 15) * 2;
-    uint32_t       raw[KW + 1];
-    for (int i = 0; i <= KW; ++i) raw[i] = (unsigned(i) <= kw) ? codes[wi + i] : 0u;
-    for (int i = 0; i < KW; ++i) {
-      uint32_t v = 0;
-      if (unsigned(i) < kw) {
-        v                   = uint32_t((((uint64_t(raw[i]) << 32) | raw[i + 1]) << sh) >> 32);
-        const unsigned have = k - 16u * unsigned(i);
-        if (have < 16) v &= ~((1u << (32 - 2 * have)) - 1u);
-      }
-      key.w[i] = v;
-    }
-    return key;
-  }
-  template <int KW>
-  WV_DEV static bool keyEq(const Key<KW>& a, const Key<KW>& b)
-  {
-    bool eq = true;
-    for (int i = 0; i < KW; ++i) eq = eq && (a.w[i] == b.w[i]);
-    return eq;
-  }
-  template <int KW>
-  WV_DEV static bool keyLess(const Key<KW>& a, const Key<KW>& b)
-  {
-    for (int i = 0; i < KW; ++i)
-      if (a.w[i] != b.w[i]) return a.w[i] < b.w[i];
-    return false;
-  }
-  template <int KW>
-  WV_DEV void keySetBase(Key<KW>& key, const unsigned i, const unsigned c) const
-  {
-    const unsigned sh = 30 - 2 * (i & 15);
-    for (int w = 0; w < KW; ++w)
-      if (unsigned(w) == (i >> 4)) key.w[w] = (key.w[w] & ~(3u << sh)) | (c << sh);
-  }
-  /// word[1..k-1] + c
-  template <int KW>
-  WV_DEV Key<KW> keyShiftAppend(const Key<KW>& key, const unsigned c) const
-  {
-    Key<KW> r;
-    for (int w = 0; w < KW; ++w) r.w[w] = (key.w[w] << 2) | ((w + 1 < KW) ? (key.w[w + 1] >> 30) : 0u);
-    keySetBase(r, k - 1, c);
-    return r;
-  }
-  /// c + word[0..k-2]
-  template <int KW>
-  WV_DEV Key<KW> keyShiftPrepend(const Key<KW>& key, const unsigned c) const
-  {
-    Key<KW> r;
-    for (int w = 0; w < KW; ++w) r.w[w] = (key.w[w] >> 2) | ((w > 0) ? (key.w[w - 1] << 30) : (c << 30));
-    // drop the base that moved to position k
-    const unsigned kw = (k + 15) >> 4;
-    for (int w = 0; w < KW; ++w) {
-      if (unsigned(w) >= kw) {
-        r.w[w] = 0;
-      } else if (unsigned(w) == kw - 1) {
-        const unsigned have = k - 16u * unsigned(w);
-        if (have < 16) r.w[w] &= ~((1u << (32 - 2 * have)) - 1u);
-      }
-    }
-    return r;
-  }
-  template <int KW>
-  WV_DEV uint32_t keyHash(const Key<KW>& key) const
-  {
-    const unsigned kw = (k + 15) >> 4;
-    uint32_t       h  = 0x811C9DC5u;
-    for (int i = 0; i < KW; ++i)
-      if (unsigned(i) < kw) h = hashMix(h, key.w[i]);
-    h ^= h >> 13;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 16;
-    return h;
-  }
-  WV_DEV uint32_t prefix32(const unsigned pb) const  // the word's first 16 bases (fewer: zero padded)
-  {
-    const unsigned wi = pb >> 4, sh = (pb & 15) * 2;
-    uint32_t       v  = codes[wi];
-    if (sh) v = (v << sh) | (codes[wi + 1] >> (32 - sh));
-    if (k < 16) v &= ~((1u << (32 - 2 * k)) - 1u);
-    return v;
-  }
-  /// byte `b` of the word at pile position pb: its bases [4 b, 4 b + 4) as eight bits, bases beyond the word length read as zero.  Comparing
-  /// words byte by byte from b = 0 is comparing their text (2-bit codes, A < C < G < T): the digits of the radix sorts below.
-  WV_DEV unsigned keyByte(const unsigned pb, const unsigned b) const
-  {
-    const unsigned at = pb + 4 * b, wi = at >> 4, sh = (at & 15) * 2;
-    uint32_t       v  = codes[wi] << sh;
-    if (sh > 24) v |= codes[wi + 1] >> (32 - sh);
-    v >>= 24;
-    const unsigned have = k - 4 * b;  // (callers pass b < ceil(k / 4))
-    if (have < 4) v &= ~((1u << (8 - 2 * have)) - 1u);
-    return v;
-  }
-  WV_DEV bool windowHasN(const unsigned maskWordBase, const unsigned j) const
-  {
-    unsigned pos = j, left = k;
-    while (left > 0) {
-      const unsigned wi = pos >> 5, bit = pos & 31;
-      const unsigned take = (32 - bit < left) ? (32 - bit) : left;
-      uint32_t       m    = nmask[maskWordBase + wi] >> bit;
-      if (take < 32) m &= (1u << take) - 1u;
-      if (m) return true;
-      pos += take;
-      left -= take;
-    }
-    return false;
   }
 
   /// set `pi` (1-based, as in a slot word) of the table pass: LDS, or -- beyond LGL_POOL_CAP -- the workgroup's device-memory workspace
@@ -322,53 +199,18 @@ struct LdsGraphL {
     return ASM_NONE;
   }
 
-  WV_DEV uint64_t plShift(const unsigned locus, const unsigned i) const
-  {
-    return P.pl_chunk_shift ? P.pl_chunk_shift[3 * size_t(locus / P.chunk_loci) + i] : uint64_t(0);
-  }
-
   // ------------------------------------------------------------------------------------------------
-  // stage 0: the locus' reads -> 2 bit + N bitmap in LDS (as LdsGraph::pack; the raw bytes are staged in pool + slots)
+  // stage 0: the locus' reads -> 2 bit + N bitmap in LDS (LdsGraphBase: scanPile, fillPile; the raw bytes are staged in pool + slots).
+  // Between the two the class' own fit test: the envelope of the locus' own reads, then the pseudo reads of a later word length.
   // ------------------------------------------------------------------------------------------------
   WV_DEV bool pack(const unsigned locus)
   {
-    const unsigned rBegin = P.locus_read_begin[locus], rEnd = P.locus_read_begin[locus + 1];
-    nNormal               = rEnd - rBegin;
-    if (nNormal + 2 * P.opt.maxAssemblyCount > LGL_MAX_READS) return false;
-    W = (nNormal + 2 * P.opt.maxAssemblyCount + 63) / 64;
-    if (W == 0) W = 1;
-    const uint64_t plR = plShift(locus, 0), plC = plShift(locus, 1), plM = plShift(locus, 2);
-    unsigned       cw = 0, mw = 0, nb = 0;  // code dwords, N-bitmap dwords, bases so far
-    bool           tooLong = false;
-    for (unsigned base = 0; base < nNormal; base += 64) {
-      const unsigned r   = base + lane;
-      unsigned       len = 0;
-      if (r < nNormal) len = P.pl_codes ? P.pl_read_len[rBegin + r + plR] : unsigned(P.read_off[rBegin + r + 1] - P.read_off[rBegin + r]);
-      if (len > 0xffffu) tooLong = true;
-      const unsigned myC = (r < nNormal) ? (len + 15) / 16 + 1 : 0u;  // +1 padding dword so key fetches may read one past
-      const unsigned myM = (r < nNormal) ? (len + 31) / 32 + 1 : 0u;
-      unsigned       sc = myC, sm = myM, sb = (r < nNormal) ? len : 0u;
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned oc = wv::shfl(sc, wv::lane() - off), om = wv::shfl(sm, wv::lane() - off), ob = wv::shfl(sb, wv::lane() - off);
-        if (wv::lane() >= off) {
-          sc += oc;
-          sm += om;
-          sb += ob;
-        }
-      }
-      const unsigned cwo = cw + sc - myC, mwo = mw + sm - myM;
-      if (tw == 0 && r < nNormal && cwo <= 0xfffu && nb + sb - len <= 0xffffu) {
-        rd[r]     = cwo | ((len & 0xffffu) << 12);
-        rdm[r]    = uint16_t(mwo);
-        rstart[r] = uint16_t(nb + sb - len);
-      }
-      cw += wv::readlane(sc, 63);
-      mw += wv::readlane(sm, 63);
-      nb += wv::readlane(sb, 63);
-    }
-    if (wv::any(tooLong) || cw + 2 > LGL_MAX_PILE + 2) return false;
+    Pile s;
+    if (!scanPile(locus, s)) return false;
+    if (!lglPileFits(nNormal, P.opt.maxAssemblyCount, s.cw, s.mw, s.tooLong ? 0x10000u : 0u, s.nb, !P.pl_codes)) return false;
     // the previous word length's contigs behind the locus' own reads (:898-905): codes only, a contig holds no N
-    unsigned pcw = 0;
+    const unsigned cw = s.cw;  // the locus' own reads end here
+    unsigned       pcw = 0;
     nReads       = nNormal + nPseudo;
     pseudoPb0    = nPseudo ? 16u * cw : 0x10000u;
     if (nPseudo) {
@@ -381,105 +223,17 @@ struct LdsGraphL {
       }
       pcw = wv::readlane(sc, 63);
       if (pcw != it->codeWords || cw + pcw + 2 > LGL_MAX_PILE_ALL + 2) return false;
+      if (!lglDynFits(cw + pcw, s.mw)) return false;
       if (tw == 0 && lane < nPseudo) {
-        rd[nNormal + lane]     = (cw + sc - myC) | ((len & 0xffffu) << 12);
+        rd[nNormal + lane]     = (cw + sc - myC) | ((len & 0xffffu) << LEN_SH);
         rdm[nNormal + lane]    = 0;
         rstart[nNormal + lane] = 0;
       }
     }
-    const unsigned cwN = cw;  // the locus' own reads end here
-    cw += pcw;
-    const unsigned cwPad = (cw + 2 + 3) & ~3u, mwPad = (mw + 2 + 3) & ~3u;
-    if (cwPad + mwPad > LGL_DYN_DWORDS || 4 * cwPad + LGL_MAX_NODES + 16 > 4 * LGL_DYN_DWORDS) return false;
-    if (!P.pl_codes && nb + 64 > LGL_STAGE_BYTES) return false;
-    codeWords = cw + 2;
-    nmask     = codes + cwPad;
-    for (unsigned i = tid(); i < pcw; i += nThreads()) codes[cwN + i] = G.parena[it->off + i];
-    cntId     = reinterpret_cast<uint8_t*>(codes + cwPad);  // (the N bitmap is dead once the reads' offsets are known)
-    for (unsigned i = tid(); i < mw + 2; i += nThreads()) nmask[i] = 0;
-    if (tid() == 0) hdr[LGL_H_FLAG] = 0;
-    teamSync();
-    if (P.pl_codes) {  // packed piles arrive in this layout: copy, 8 lanes per read
-      for (unsigned base = 8 * tw; base < nNormal; base += 8 * tn) {
-        const unsigned r = base + (lane >> 3);
-        if (r >= nNormal) continue;
-        const unsigned  d = rd[r], cwo = d & 0xfffu, len = (d >> 12) & 0xffffu, mwo = rdm[r];
-        const unsigned  nCw = (len + 15) / 16, nMw = (len + 31) / 32;
-        const uint32_t* sc  = P.pl_codes + (P.pl_code_off[rBegin + r + plR] + plC);
-        const uint32_t* sm  = P.pl_nmask + (P.pl_mask_off[rBegin + r + plR] + plM);
-        for (unsigned wi = (lane & 7); wi <= nCw; wi += 8) codes[cwo + wi] = (wi < nCw) ? sc[wi] : 0u;
-        bool sawN = false;
-        for (unsigned wi = (lane & 7); wi < nMw; wi += 8) {
-          const uint32_t m = sm[wi];
-          nmask[mwo + wi]  = m;
-          sawN             = sawN || (m != 0);
-        }
-        if (sawN) wv::atomic_or(&rd[r], 1u << 28);
-      }
-      if (tid() < 2) codes[cw + tid()] = 0;
-      teamSync();
-      return true;
-    }
-    bool           bad   = false;
-    const uint32_t shift = P.chunk_shift ? P.chunk_shift[locus / P.chunk_loci] : 0u;
-    // the locus' bases are one contiguous run of the input arena: 16-byte pieces into LDS, all loads in flight at once
-    char* const stage = lds + LGL_OFF_POOL;
-    unsigned    lead  = 0;
-    {
-      const uintptr_t g0 = reinterpret_cast<uintptr_t>(P.bases + P.read_off[rBegin] + shift);
-      lead               = unsigned(g0 & 15);
-      const u32x4*   gsrc    = reinterpret_cast<const u32x4*>(g0 - lead);
-      const unsigned nChunks = (lead + nb + 15) / 16 + 1;  // (+1: the byte funnel reads up to four bytes past a read's last dword; the arena is padded)
-      for (unsigned c = tid(); c < nChunks; c += nThreads()) reinterpret_cast<u32x4*>(stage)[c] = gsrc[c];
-    }
-    teamSync();
-    // 8 lanes per read: lane (g, i) converts code dwords i, i+8, ... of read (base + g)
-    for (unsigned base = 8 * tw; base < nNormal; base += 8 * tn) {
-      const unsigned r = base + (lane >> 3);
-      if (r >= nNormal) continue;
-      const char*    src = stage + lead + rstart[r];
-      const unsigned d = rd[r], cwo = d & 0xfffu, len = (d >> 12) & 0xffffu, mwo = rdm[r];
-      const unsigned nCw = (len + 15) / 16 + 1;
-      bool           sawN = false;
-      for (unsigned wi = (lane & 7); wi < nCw; wi += 8) {
-        uint32_t code = 0, nbits = 0;
-        if (wi * 16 < len) {
-          // 16 bases = five aligned dword reads + a byte funnel
-          const uintptr_t addr = reinterpret_cast<uintptr_t>(src + wi * 16);
-          const uint32_t* ap   = reinterpret_cast<const uint32_t*>(addr & ~uintptr_t(3));
-          const unsigned  sh   = unsigned(addr & 3) * 8;
-          uint32_t        dw[5];
-          for (int q = 0; q < 5; ++q) dw[q] = ap[q];
-          for (unsigned q = 0; q < 4; ++q) {
-            const uint32_t four = sh ? ((dw[q] >> sh) | (dw[q + 1] << (32 - sh))) : dw[q];
-            for (unsigned b4 = 0; b4 < 4; ++b4) {
-              const unsigned b = q * 4 + b4;
-              const unsigned i = wi * 16 + b;
-              unsigned       c = 0;
-              if (i < len) {
-                c = baseCode(uint8_t(four >> (8 * b4)));
-                if (c == 5) bad = true;
-                if (c >= 4) {
-                  nbits |= (1u << b);
-                  c = 0;
-                }
-              }
-              code |= c << (30 - 2 * b);
-            }
-          }
-        }
-        codes[cwo + wi] = code;
-        if (nbits) {
-          wv::atomic_or(&nmask[mwo + (wi >> 1)], (wi & 1) ? (nbits << 16) : nbits);
-          sawN = true;
-        }
-      }
-      if (sawN) wv::atomic_or(&rd[r], 1u << 28);
-    }
-    if (tid() < 2) codes[cw + tid()] = 0;
-    if (wv::any(bad) && lane == 0) wv::atomic_or(&hdr[LGL_H_FLAG], 1u);  // bytes outside {A,C,G,T,N}: the general path decides what is exact
-    teamSync();
-    return wv::atomic_load(&hdr[LGL_H_FLAG]) == 0;
+    for (unsigned i = tid(); i < pcw; i += nThreads()) codes[cw + i] = G.parena[it->off + i];
+    s.cw += pcw;
+    cntId = reinterpret_cast<uint8_t*>(codes + ((s.cw + 2 + 3) & ~3u));  // (behind the codes: the N bitmap is dead once the reads' offsets are known)
+    return fillPile(locus, s);
   }
 
   // ------------------------------------------------------------------------------------------------
@@ -618,17 +372,6 @@ struct LdsGraphL {
     const unsigned lo = 64 * q;
     return (nNormal >= lo + 64) ? ~uint64_t(0) : ((nNormal > lo) ? ((uint64_t(1) << (nNormal - lo)) - 1) : uint64_t(0));
   }
-  /// read that owns packed base index pb (the reads' code offsets ascend)
-  WV_DEV unsigned readOfPb(const unsigned pb) const
-  {
-    const unsigned cwd = pb >> 4;
-    unsigned       lo = 0, hi = nReads;  // rd[lo].cwo <= cwd < rd[hi].cwo
-    while (hi - lo > 1) {
-      const unsigned mid = (lo + hi) >> 1;
-      if ((rd[mid] & 0xfffu) <= cwd) lo = mid; else hi = mid;
-    }
-    return lo;
-  }
 
   // ------------------------------------------------------------------------------------------------
   // the reads' offsets on a common axis (LdsGraph::readOffsets, four reads per lane): anchors -> forest -> pointer doubling ->
@@ -638,70 +381,9 @@ struct LdsGraphL {
   WV_DEV void readOffsets()
   {
     if (tw == 0) {
-      const uint32_t* anch = reinterpret_cast<const uint32_t*>(lds + LGL_OFF_ANCH);
-      int32_t*        off  = reinterpret_cast<int32_t*>(lds + LGL_OFF_ANCH) + LGL_MAX_READS;
-      uint8_t*        par  = reinterpret_cast<uint8_t*>(lds + LGL_OFF_PAR);
-      int32_t         myOff[RPL];
-      unsigned        myPar[RPL], myRoot[RPL];
-      for (unsigned h = 0; h < RPL; ++h) {
-        const unsigned r = lane + 64 * h;
-        myOff[h]  = 0;
-        myPar[h]  = r;
-        myRoot[h] = r;
-        if (r < nReads) {
-          const uint32_t a = anch[r];
-          if (a != LG_NO_ANCHOR) {
-            const unsigned apb = a & 0xffffu, j = a >> 16;
-            const unsigned r0  = readOfPb(apb);
-            myPar[h] = r0;
-            myOff[h] = int32_t(apb - 16u * (rd[r0] & 0xfffu)) - int32_t(j);
-          }
-        }
-      }
-      wv::sync();
-      for (unsigned h = 0; h < RPL; ++h) {
-        off[lane + 64 * h] = myOff[h];
-        par[lane + 64 * h] = uint8_t(myPar[h]);
-      }
-      wv::sync();
-      for (int round = 0; round < 8; ++round) {
-        int32_t  po[RPL];
-        unsigned pp[RPL];
-        for (unsigned h = 0; h < RPL; ++h) {
-          po[h] = off[myPar[h]];
-          pp[h] = par[myPar[h]];
-        }
-        wv::sync();
-        for (unsigned h = 0; h < RPL; ++h) {
-          const unsigned r = lane + 64 * h;
-          if (myPar[h] != r) {  // (a root keeps its offset)
-            myOff[h] += po[h];
-            if (pp[h] == myPar[h]) {  // the parent is a root: done after this addition
-              off[r]    = myOff[h];
-              par[r]    = uint8_t(r);
-              myRoot[h] = myPar[h];
-              myPar[h]  = r;
-            } else {
-              off[r]   = myOff[h];
-              par[r]   = uint8_t(pp[h]);
-              myPar[h] = pp[h];
-            }
-          }
-        }
-        wv::sync();
-      }
-      // (myRoot is the read the offset was completed through -- the root for the root's children, a finished inner read for the
-      // reads below: the roots proper by pointer jumping)
-      uint8_t* rootOf = reinterpret_cast<uint8_t*>(lds + LGL_OFF_WHIST);  // (the histograms are not in use before the sort)
-      for (unsigned h = 0; h < RPL; ++h) rootOf[lane + 64 * h] = uint8_t(myRoot[h]);
-      wv::sync();
-      for (int round = 0; round < 8; ++round) {
-        unsigned up[RPL];
-        for (unsigned h = 0; h < RPL; ++h) up[h] = rootOf[rootOf[lane + 64 * h]];
-        wv::sync();
-        for (unsigned h = 0; h < RPL; ++h) rootOf[lane + 64 * h] = uint8_t(up[h]);
-        wv::sync();
-      }
+      int32_t  myOff[RPL];  // (the trees are tied together from the arrays in LDS: these go unused)
+      unsigned myRoot[RPL];
+      anchorForest(myOff, myRoot);
     }
     teamSync();
     // ---- the trees tied together.  Sixteen waves insert reads at once, so which of two overlapping reads "was first" is a race and a
@@ -711,10 +393,10 @@ struct LdsGraphL {
     // links one after the other (each with the offsets as they are by then).  Any phi that rises along every edge proves acyclicity,
     // so nothing here can make the proof unsound.
     if (!(G.flags & LG_FLAG_NO_RESCUE)) {
-      uint8_t*  rootOf = reinterpret_cast<uint8_t*>(lds + LGL_OFF_WHIST);
+      uint8_t*  rootOf = rootOfRead();
       uint8_t*  roots  = rootOf + LGL_MAX_READS;                                   // [256] the roots, ascending
       uint32_t* link   = reinterpret_cast<uint32_t*>(rootOf + 2 * LGL_MAX_READS);  // [256][2] {read x | position j << 16, first occurrence} per root
-      int32_t*  off    = reinterpret_cast<int32_t*>(lds + LGL_OFF_ANCH) + LGL_MAX_READS;
+      int32_t*  off    = readOff();
       for (unsigned round = 0; round < 3; ++round) {
         // the roots (every wave computes the same list; wave 0 writes it)
         unsigned nRoots = 0;
@@ -835,7 +517,7 @@ struct LdsGraphL {
     }
     // (rdm is dead after the table pass: its bytes take the offsets; one that does not fit 16 bits only loses the proof)
     if (tw == 0) {
-      const int32_t* off = reinterpret_cast<const int32_t*>(lds + LGL_OFF_ANCH) + LGL_MAX_READS;
+      const int32_t* off = readOff();
       for (unsigned h = 0; h < RPL; ++h) {
         const int32_t v     = off[lane + 64 * h];
         roff[lane + 64 * h] = int16_t((v > 30000) ? 30000 : ((v < -30000) ? -30000 : v));
@@ -921,50 +603,12 @@ struct LdsGraphL {
       for (unsigned j = 0; j < SORT_IT; ++j)
         if (sv[j] != 0xffffffffu) wv::atomic_add(&myHist[dv[j]], 1u);
       teamSync();
-      // per digit: running offsets over the waves, totals; then the digit bases (four quarters of 64 digits, one wave each)
-      for (unsigned q = tw; q < 4; q += tn) {
-        const unsigned d   = 64 * q + lane;
-        unsigned       run = 0;
-        for (unsigned w = 0; w < tn; ++w) {
-          const unsigned c   = whist[256 * w + d];
-          whist[256 * w + d] = run;
-          run += c;
-        }
-        unsigned inc = run;
-        for (int off = 1; off < 64; off <<= 1) {
-          const unsigned o = wv::shfl(inc, int(lane) - off);
-          if (int(lane) >= off) inc += o;
-        }
-        dbase[d] = inc - run;  // exclusive inside the quarter
-        if (lane == 63) hdr[LGL_H_TOT + q] = inc;
-      }
-      teamSync();
-      for (unsigned q = tw; q < 4; q += tn) {
-        unsigned before = 0;
-        for (unsigned p = 0; p < q; ++p) before += hdr[LGL_H_TOT + p];
-        dbase[64 * q + lane] += before;
-      }
-      teamSync();
+      radixDigitBases(whist);
 #pragma unroll
       for (unsigned j = 0; j < SORT_IT; ++j) {
         if (c0 + 64 * j >= c1) break;  // (wave-uniform)
         const bool     valid = sv[j] != 0xffffffffu;
-        const unsigned slot  = valid ? sv[j] : 0u;
-        const unsigned d     = dv[j];
-        uint64_t       peers = wv::ballot(valid);
-        for (int bit = 0; bit < 8; ++bit) {
-          const bool     on = (d >> bit) & 1u;
-          const uint64_t m  = wv::ballot(valid && on);
-          peers &= on ? m : ~m;
-        }
-        unsigned base = 0;
-        if (valid) base = dbase[d] + myHist[d];
-        wv::sync();
-        if (valid) {
-          dst[base + unsigned(wv::popc(peers & ((uint64_t(1) << lane) - 1)))] = uint16_t(slot);
-          if ((peers >> lane) == 1u) myHist[d] += unsigned(wv::popc(peers));  // the highest lane of the digit's group
-        }
-        wv::sync();
+        radixScatter(valid, valid ? sv[j] : 0u, dv[j], dst, myHist);
       }
       teamSync();
       if (pass == nb && tid() == 0) {
@@ -1159,48 +803,13 @@ struct LdsGraphL {
       if (i < c1) wv::atomic_add(&myHist[digitOf(src[i])], 1u);
     }
     teamSync();
-    for (unsigned q = tw; q < 4; q += tn) {
-      const unsigned d   = 64 * q + lane;
-      unsigned       run = 0;
-      for (unsigned w = 0; w < tn; ++w) {
-        const unsigned c  = hist[256 * w + d];
-        hist[256 * w + d] = run;
-        run += c;
-      }
-      unsigned inc = run;
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned o = wv::shfl(inc, int(lane) - off);
-        if (int(lane) >= off) inc += o;
-      }
-      dbase[d] = inc - run;
-      if (lane == 63) hdr[LGL_H_TOT + q] = inc;
-    }
-    teamSync();
-    for (unsigned q = tw; q < 4; q += tn) {
-      unsigned before = 0;
-      for (unsigned p = 0; p < q; ++p) before += hdr[LGL_H_TOT + p];
-      dbase[64 * q + lane] += before;
-    }
-    teamSync();
+    radixDigitBases(hist);
     for (unsigned i0 = c0; i0 < c1; i0 += 64) {
       const unsigned i     = i0 + lane;
       const bool     valid = i < c1;
       const unsigned id    = valid ? unsigned(src[i]) : 0u;
       const unsigned d     = valid ? digitOf(id) : 0u;
-      uint64_t       peers = wv::ballot(valid);
-      for (int bit = 0; bit < 8; ++bit) {
-        const bool     on = (d >> bit) & 1u;
-        const uint64_t m  = wv::ballot(valid && on);
-        peers &= on ? m : ~m;
-      }
-      unsigned base = 0;
-      if (valid) base = dbase[d] + myHist[d];
-      wv::sync();
-      if (valid) {
-        dst[base + unsigned(wv::popc(peers & ((uint64_t(1) << lane) - 1)))] = uint16_t(id);
-        if ((peers >> lane) == 1u) myHist[d] += unsigned(wv::popc(peers));
-      }
-      wv::sync();
+      radixScatter(valid, id, d, dst, myHist);
     }
     teamSync();
   }
@@ -1544,38 +1153,8 @@ struct LdsGraphL {
     uint16_t*      gSpec = reinterpret_cast<uint16_t*>(slab + SL.spec);
     const unsigned nSpec = speculationList(gSpec, !acyclic);
     tick(2, 6);
-    // the rest of the slab
-    FRec8* gRec = reinterpret_cast<FRec8*>(slab + SL.recs);
-    for (unsigned i = tid(); i < nNodes; i += nThreads()) gRec[i] = nodes[i];
-    const unsigned nSib = wv::atomic_load(&hdr[LGL_H_NSIB]), nSovf = wv::atomic_load(&hdr[LGL_H_NSOVF]), nPovf = wv::atomic_load(&hdr[LGL_H_NPOVF]);
-    {
-      // the three side tables lie back to back in LDS and in the slab (fixed capacities)
-      const uint16_t* tsrc = reinterpret_cast<const uint16_t*>(lds + LGL_OFF_SIB);
-      uint16_t*       tdst = reinterpret_cast<uint16_t*>(slab + SL.sib);
-      for (unsigned i = tid(); i < 4 * (LG_SIB_CAP + 2 * LGL_OVF_CAP); i += nThreads()) tdst[i] = tsrc[i];
-    }
-    uint32_t* gCodes = reinterpret_cast<uint32_t*>(slab + SL.codes);
-    for (unsigned i = tid(); i < codeWords; i += nThreads()) gCodes[i] = codes[i];
+    writeSlab(locus, off, SL, nodes, nSpec, need, acyclic, nPseudo, nCorePeel);  // (nCore -- repeat_big_kernel: the peel's core; it leaves the number of words on cycles there)
     if (tid() == 0) {
-      LgHdr h;
-      h.nNodes    = nNodes;
-      h.nFat      = nFat;
-      h.k         = k;
-      h.nNormal   = nNormal;
-      h.nEligible = nEligible;
-      h.nSpec     = nSpec;
-      h.nSib      = nSib;
-      h.codeWords = codeWords;
-      h.W         = W;
-      h.need      = need;
-      h.nSovf     = nSovf;
-      h.nPovf     = nPovf;
-      h.acyclic   = acyclic ? 1u : 0u;
-      h.nPseudo   = nPseudo;
-      h.cyclic    = 0;
-      h.nCore     = nCorePeel;  // (repeat_big_kernel: the peel's core; it leaves the number of words on cycles here)
-      *reinterpret_cast<LgHdr*>(slab) = h;
-      G.slab_off[locus]               = off;
       if (toRepeat)
         G.cyc_ids[wv::atomic_add(G.cyc_count, 1u)] = locus;
       else
@@ -1629,30 +1208,8 @@ struct LdsGraphL {
 template <int MAXKW>
 WV_KERNEL_WG(LGL_WAVES) WV_WAVES_PER_SIMD(4) void graph_big_kernel(const LgArgs A)
 {
-  const AsmParams& P = A.P;
-  const LgParams&  G = A.G;
-  char*          lds = wv::lds_single();
-  uint32_t*      hdr = reinterpret_cast<uint32_t*>(lds + LGL_OFF_HDR);
-  const unsigned tw  = unsigned(wv::wave_in_wg());
-  const unsigned nLoci = P.n_loci_dev ? wv::first(wv::atomic_load(P.n_loci_dev)) : P.n_loci;  // (later rounds: the previous round's list)
-  while (true) {
-    if (tw == 0 && wv::lane() == 0) hdr[LGL_H_SLOT] = wv::atomic_add(P.counter, 1u);
-    wv::sync();
-    wv::wg_barrier();
-    const unsigned slot = wv::first(wv::atomic_load(&hdr[LGL_H_SLOT]));
-    if (slot >= nLoci) break;
-    const unsigned locus   = P.locus_ids ? P.locus_ids[slot] : slot;
-    const bool     arrived = !P.upload_chunks_done || asmWaitUploaded(P, locus);
-    bool           ok      = false;
-    if (arrived) {
-      LdsGraphL g(P, G, lds);
-      ok = g.template run<MAXKW>(locus);
-    }
-    wv::sync();
-    if (tw == 0 && !ok && wv::lane() == 0) P.punt_ids[wv::atomic_add(P.punt_count, 1u)] = locus;
-    wv::sync();
-    wv::wg_barrier();  // (the slot word is rewritten next)
-  }
+  const unsigned nLoci = A.P.n_loci_dev ? wv::first(wv::atomic_load(A.P.n_loci_dev)) : A.P.n_loci;  // (later rounds: the previous round's list)
+  lgGraphLoop<LdsGraphL, MAXKW>(A, nLoci);
 }
 
 #if MANTA_TU != MANTA_TU_ALL

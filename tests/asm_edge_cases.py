@@ -48,7 +48,7 @@ LGL_CLASS_BYTES = (81920, 163840)  # contig_big_kernel's classes.  The second is
 def header_constants():
     """the same names read from the sources (simple `static const unsigned NAME = <integer>;` lines, plus the two derived offsets)"""
     out = {}
-    for f in ("asm_lds.hpp", "asm_lds_big.hpp", "asm_contig.hpp"):
+    for f in ("asm_lds.hpp", "asm_lds_base.hpp", "asm_lds_big.hpp", "asm_contig.hpp"):
         for m in re.finditer(r"static const unsigned (\w+)\s*=\s*(\d+);", open(os.path.join(CSRC, f)).read()):
             out[m.group(1)] = int(m.group(2))
     return out

@@ -217,6 +217,192 @@ static int alignBatch(
   }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// what the entry points of the two fused pipelines share
+// ------------------------------------------------------------------------------------------------------
+namespace {
+
+/// host -> device copies of an upload's references and cuts, listed by refCopies() and queued behind the reads
+struct RefCopies {
+  struct Copy {
+    void*       dst;
+    const void* src;
+    size_t      bytes;
+  } c[5];
+  int  n = 0;
+  void add(void* dst, const void* src, size_t bytes) { c[n++] = Copy{dst, src, bytes}; }
+  void queue() const
+  {
+    for (int i = 0; i < n; ++i) rt::h2d(c[i].dst, c[i].src, c[i].bytes);
+  }
+};
+
+/// per pipeline: validates the reference windows and cuts of an upload, sizes their device buffers and lists the copies
+int refCopies(manta_smallsv* b, const char* who, uint32_t n_loci, RefCopies& out, const uint8_t* refs, const uint64_t* ref_off, const manta_ref_cuts_t* cuts)
+{
+  b->refBytes = ref_off[n_loci];
+  b->maxRef   = 0;
+  for (uint32_t l = 0; l < n_loci; ++l) {
+    if (ref_off[l + 1] < ref_off[l]) return fail(b->ctx, MANTA_E_INVALID_ARG, std::string(who) + ": ref_off not monotone");
+    b->maxRef = std::max<uint64_t>(b->maxRef, ref_off[l + 1] - ref_off[l]);
+    if (cuts[l].leading_cut < 0 || cuts[l].trailing_cut < 0 || cuts[l].max_leading_cut < 0 || cuts[l].max_trailing_cut < 0)
+      return fail(b->ctx, MANTA_E_INVALID_ARG, std::string(who) + ": negative reference cut");
+  }
+  static_assert(sizeof(SmallSvCuts) == sizeof(manta_ref_cuts_t), "cuts layout");
+  out.add(b->dRefs.as<uint8_t>(b->refBytes + 16), refs, b->refBytes);
+  out.add(b->dRefOff.as<uint64_t>(n_loci + 1), ref_off, sizeof(uint64_t) * (n_loci + 1));
+  out.add(b->dCuts.as<SmallSvCuts>(n_loci), cuts, sizeof(SmallSvCuts) * n_loci);
+  return MANTA_OK;
+}
+
+int refCopies(manta_spanning* b, const char* who, uint32_t n_loci, RefCopies& out, const uint8_t* refs1, const uint64_t* ref1_off, const uint8_t* refs2,
+              const uint64_t* ref2_off, const manta_jump_cuts_t* cuts)
+{
+  b->ref1Bytes = ref1_off[n_loci];
+  b->ref2Bytes = ref2_off[n_loci];
+  for (uint32_t l = 0; l < n_loci; ++l) {
+    if (ref1_off[l + 1] < ref1_off[l] || ref2_off[l + 1] < ref2_off[l])
+      return fail(b->ctx, MANTA_E_INVALID_ARG, std::string(who) + ": reference offsets not monotone");
+    const manta_jump_cuts_t& c(cuts[l]);
+    if (c.align1_leading_cut < 0 || c.align1_trailing_cut < 0 || c.align2_leading_cut < 0 || c.align2_trailing_cut < 0)
+      return fail(b->ctx, MANTA_E_INVALID_ARG, std::string(who) + ": negative reference cut");
+  }
+  static_assert(sizeof(JumpCuts) == sizeof(manta_jump_cuts_t), "cuts layout");
+  out.add(b->dRefs1.as<uint8_t>(b->ref1Bytes + 16), refs1, b->ref1Bytes);
+  out.add(b->dRef1Off.as<uint64_t>(n_loci + 1), ref1_off, sizeof(uint64_t) * (n_loci + 1));
+  out.add(b->dRefs2.as<uint8_t>(b->ref2Bytes + 16), refs2, b->ref2Bytes);
+  out.add(b->dRef2Off.as<uint64_t>(n_loci + 1), ref2_off, sizeof(uint64_t) * (n_loci + 1));
+  out.add(b->dCuts.as<JumpCuts>(n_loci), cuts, sizeof(JumpCuts) * n_loci);
+  b->hostCuts.assign(reinterpret_cast<const JumpCuts*>(cuts), reinterpret_cast<const JumpCuts*>(cuts) + n_loci);
+  return MANTA_OK;
+}
+
+/// The four upload calls (`who`; the caller has checked its pointers): plan the assembler, validate the references, then the reads and
+/// behind them the references.  Streamed (whole-batch calls, `mayStream`): the reads travel in chunks on the copy stream behind the
+/// running assembler; the assembler does not read the reference windows, so they follow on the same stream and the schedule kernel waits
+/// for them (refsReady) -- nothing but the small per-read arrays is waited for here.  Otherwise everything is on the device at return.
+template <typename Pipe, typename... Refs>
+int pipeUpload(Pipe* b, const char* who, uint32_t n_loci, const ReadsIn& rd, bool mayStream, Refs... refs)
+{
+  manta_ctx_t* ctx = b->ctx;
+  try {
+    rt::setDevice(ctx->deviceId);  // the calling thread may have another device current (multi-GPU hosts)
+    rt::ScopedStream onStream(b->main);
+    b->uploaded   = false;
+    b->refsOnCopy = false;
+    const double tP0      = nowMs();
+    const bool   streamed = mayStream && b->streamUploads && !std::getenv("MANTA_AMD_NO_STREAM_UPLOAD");
+    // a streamed upload of read bases starts their DMA before anything else (small-SV): plan()'s pass over the read offsets runs beside it
+    const bool earlyStream = Pipe::kEarlyStream && streamed && !rd.piles && !std::getenv("MANTA_AMD_NO_EARLY_STREAM");  // A/B knob (read per call: the tests flip it)
+    // (the ticket: chunks in flight.  Every return before uploadStreamed() takes it drops it, which drains the copy stream)
+    std::optional<ChunkStream::Ticket> early = earlyStream ? b->asmStage.startStream(n_loci, rd.bases, rd.read_off, rd.locus_read_begin, b->copy) : std::nullopt;
+    int rc = b->asmStage.plan(b->opt, n_loci, rd.piles ? nullptr : rd.read_off, rd.locus_read_begin, rd.piles ? rd.piles->read_len : nullptr);
+    if (rc != MANTA_OK) return rc;
+    const double tP1 = nowMs();
+    b->nLoci         = n_loci;
+    RefCopies copies;
+    rc = refCopies(b, who, n_loci, copies, refs...);
+    if (rc != MANTA_OK) return rc;
+    b->refsOnCopy = streamed;
+    if (streamed) {
+      if (rd.piles)
+        b->asmStage.uploadPilesStreamed(*rd.piles, b->copy);
+      else
+        b->asmStage.uploadStreamed(rd.bases, rd.read_off, rd.locus_read_begin, b->copy, std::move(early));  // syncs the small copies, returns with the bases in flight
+      rt::ScopedStream onCopy(b->copy);
+      copies.queue();
+      b->refsReady.record();
+    } else {
+      if (rd.piles)
+        b->asmStage.uploadPiles(*rd.piles);
+      else
+        b->asmStage.upload(rd.bases, rd.read_off, rd.locus_read_begin);
+      copies.queue();
+      rt::sync();
+    }
+    if (std::getenv("MANTA_AMD_DEBUG_TIMING"))
+      std::fprintf(stderr, "manta_amd: %s plan %.2f ms, upload (%s) %.2f ms\n", who + 6, tP1 - tP0, b->asmStage.chunks.active() ? "streamed" : "blocking", nowMs() - tP1);
+    b->uploaded = true;
+    return MANTA_OK;
+  } catch (const std::exception& e) {
+    drainCopyStream(b);  // (chunks uploadStreamed() had taken over, with the reference copies behind them)
+    return fail(ctx, MANTA_E_HIP, e.what());
+  }
+}
+
+/// The end of a pipeline run, behind pack_results_kernel and evAlign: a whole-batch call's staging is queued behind the last kernel (no
+/// wake-up in between) and the host does its share of the assembler's outputs while the aligners have ~2 ms to go; then the device is
+/// waited for, the align gate opens and the stages' times are read.
+void finishRun(PipeBase* b, const bool earlyStage, GateLock& alignOnly)
+{
+  AsmStage& as(b->asmStage);
+  if (b->stageBehindRun) pipeStageEnqueue(b);
+  if (earlyStage) {
+    b->evEarlyStaged.sync();
+    as.finishEarly();
+    b->whileAligning();
+  }
+  rt::sync();
+  alignOnly.release();
+  if (as.chunks.active()) {  // every chunk was consumed by the kernel, so this returns at once; it closes the copy stream's error state
+    rt::ScopedStream onCopy(b->copy);
+    rt::sync();
+  }
+  b->stats.assemble_ms = rt::elapsedMs(b->evStart, b->evAsm);
+  b->stats.schedule_ms = rt::elapsedMs(b->evAsm, b->evSched);
+  b->stats.align_ms    = rt::elapsedMs(b->evSched, b->evAlign);
+  b->stats.total_ms    = rt::elapsedMs(b->evStart, b->evAlign);
+}
+
+/// manta_*_stats, manta_*_output_sizes, manta_*_download: one body each
+int pipeStats(const PipeBase* b, manta_smallsv_stats_t* stats)
+{
+  if (!b || !stats) return MANTA_E_INVALID_ARG;
+  *stats = b->stats;
+  return MANTA_OK;
+}
+
+template <typename Pipe>
+int pipeOutputSizes(const Pipe* b, uint64_t* contigs, uint64_t* seq_bytes, uint64_t* bits_words, uint64_t* cigar_words)
+{
+  if (!b || !contigs || !seq_bytes || !bits_words || !cigar_words) return MANTA_E_INVALID_ARG;
+  if (!b->ran) return fail(b->ctx, MANTA_E_INVALID_ARG, std::string("manta_") + Pipe::kFamily + "_output_sizes: run first");
+  try {
+    rt::setDevice(b->ctx->deviceId);  // the calling thread may have another device current (multi-GPU hosts)
+    rt::ScopedStream onStream(const_cast<Pipe*>(b)->main);
+    b->asmStage.outputSizes(*contigs, *seq_bytes, *bits_words);
+    uint64_t cig = 0;  // (the schedule kernel's allocator of the CIGAR scratch: two words of dSmall)
+    rt::d2h(&cig, static_cast<const uint32_t*>(b->dSmall.p) + Pipe::kCigarUsedWord, sizeof(cig));
+    *cigar_words = cig + 64;
+    return MANTA_OK;
+  } catch (const std::exception& e) {
+    return fail(b->ctx, MANTA_E_HIP, e.what());
+  }
+}
+
+template <typename Pipe>
+int pipeDownload(Pipe* b, manta_asm_locus_result_t* loci, manta_asm_contig_t* contigs, typename Pipe::Alignment* alignments, uint64_t contigs_cap,
+                 uint8_t* seq_arena, uint64_t seq_arena_cap, uint64_t* seq_arena_used, uint64_t* bits_arena, uint64_t bits_arena_cap,
+                 uint64_t* bits_arena_used, uint32_t* cigar_arena, uint64_t cigar_arena_cap, uint64_t* cigar_arena_used)
+{
+  if (!b) return MANTA_E_INVALID_ARG;
+  manta_ctx_t*      ctx = b->ctx;
+  const std::string who = std::string("manta_") + Pipe::kFamily + "_download";
+  if (!b->ran) return fail(ctx, MANTA_E_INVALID_ARG, who + ": run first");
+  if (!loci || !contigs || !alignments || !seq_arena || !bits_arena || !cigar_arena) return fail(ctx, MANTA_E_INVALID_ARG, who + ": null argument");
+  try {
+    rt::setDevice(ctx->deviceId);  // the calling thread may have another device current (multi-GPU hosts)
+    rt::ScopedStream onStream(b->main);
+    pipeStage(b);
+    return compact(b, loci, contigs, alignments, 0, contigs_cap, seq_arena, seq_arena_cap, 0, seq_arena_used, bits_arena, bits_arena_cap, 0,
+                   bits_arena_used, cigar_arena, cigar_arena_cap, 0, cigar_arena_used);
+  } catch (const std::exception& e) {
+    return fail(ctx, MANTA_E_HIP, e.what());
+  }
+}
+
+}  // namespace
+
 extern "C" {
 
 int manta_align_batch(
@@ -419,111 +605,21 @@ int manta_smallsv_upload(
     const uint8_t* refs, const uint64_t* ref_off, const manta_ref_cuts_t* cuts)
 {
   if (!b) return MANTA_E_INVALID_ARG;
-  manta_ctx_t* ctx = b->ctx;
   if (n_loci == 0 || !bases || !read_off || !locus_read_begin || !refs || !ref_off || !cuts)
-    return fail(ctx, MANTA_E_INVALID_ARG, "manta_smallsv_upload: null argument or empty batch");
-  try {
-    rt::setDevice(ctx->deviceId);  // the calling thread may have another device current (multi-GPU hosts)
-    rt::ScopedStream onStream(b->main);
-    b->uploaded = false;
-    const double tP0 = nowMs();
-    const bool streamed = b->streamUploads && !std::getenv("MANTA_AMD_NO_STREAM_UPLOAD");
-    // a streamed upload starts the DMA of the read bases before anything else: plan()'s pass over the read offsets runs beside it
-    const bool noEarlyStream = std::getenv("MANTA_AMD_NO_EARLY_STREAM") != nullptr;  // A/B knob (read per call: the tests flip it)
-    // (the ticket: chunks in flight.  Every return before uploadStreamed() takes it drops it, which drains the copy stream)
-    std::optional<ChunkStream::Ticket> early = (streamed && !noEarlyStream) ? b->asmStage.startStream(n_loci, bases, read_off, locus_read_begin, b->copy) : std::nullopt;
-    int rc      = b->asmStage.plan(b->opt, n_loci, read_off, locus_read_begin);
-    if (rc != MANTA_OK) return rc;
-    const double tP1 = nowMs();
-    b->nLoci    = n_loci;
-    b->refBytes = ref_off[n_loci];
-    b->maxRef   = 0;
-    for (uint32_t l = 0; l < n_loci; ++l) {
-      if (ref_off[l + 1] < ref_off[l]) return fail(ctx, MANTA_E_INVALID_ARG, "manta_smallsv_upload: ref_off not monotone");
-      b->maxRef = std::max<uint64_t>(b->maxRef, ref_off[l + 1] - ref_off[l]);
-      if (cuts[l].leading_cut < 0 || cuts[l].trailing_cut < 0 || cuts[l].max_leading_cut < 0 || cuts[l].max_trailing_cut < 0)
-        return fail(ctx, MANTA_E_INVALID_ARG, "manta_smallsv_upload: negative reference cut");
-    }
-    uint8_t*  dRefs   = b->dRefs.as<uint8_t>(b->refBytes + 16);
-    uint64_t* dRefOff = b->dRefOff.as<uint64_t>(n_loci + 1);
-    auto*     dCuts   = b->dCuts.as<SmallSvCuts>(n_loci);
-    static_assert(sizeof(SmallSvCuts) == sizeof(manta_ref_cuts_t), "cuts layout");
-    b->refsOnCopy       = streamed;
-    if (streamed) {
-      // the assembler does not read the reference windows: they travel on the copy stream BEHIND the read bases and the
-      // schedule kernel waits for them (smallsvRunImpl); nothing but the small per-read arrays is waited for here
-      b->asmStage.uploadStreamed(bases, read_off, locus_read_begin, b->copy, std::move(early));  // syncs the small copies, returns with the bases in flight
-      rt::ScopedStream onCopy(b->copy);
-      rt::h2d(dRefs, refs, b->refBytes);
-      rt::h2d(dRefOff, ref_off, sizeof(uint64_t) * (n_loci + 1));
-      rt::h2d(dCuts, cuts, sizeof(SmallSvCuts) * n_loci);
-      b->refsReady.record();
-    } else {
-      rt::h2d(dRefs, refs, b->refBytes);
-      rt::h2d(dRefOff, ref_off, sizeof(uint64_t) * (n_loci + 1));
-      rt::h2d(dCuts, cuts, sizeof(SmallSvCuts) * n_loci);
-      b->asmStage.upload(bases, read_off, locus_read_begin);
-      rt::sync();
-    }
-    if (std::getenv("MANTA_AMD_DEBUG_TIMING"))
-      std::fprintf(stderr, "manta_amd: smallsv_upload plan %.2f ms, upload (%s) %.2f ms\n", tP1 - tP0, b->asmStage.chunks.active() ? "streamed" : "blocking", nowMs() - tP1);
-    b->uploaded = true;
-    return MANTA_OK;
-  } catch (const std::exception& e) {
-    drainCopyStream(b);  // (chunks uploadStreamed() had taken over, with the reference copies behind them)
-    return fail(ctx, MANTA_E_HIP, e.what());
-  }
+    return fail(b->ctx, MANTA_E_INVALID_ARG, "manta_smallsv_upload: null argument or empty batch");
+  return pipeUpload(b, "manta_smallsv_upload", n_loci, ReadsIn{bases, read_off, locus_read_begin, nullptr}, true, refs, ref_off, cuts);
 }
-
 
 int manta_smallsv_upload_piles(
     manta_smallsv_t* b, uint32_t n_loci, const manta_packed_piles_t* piles, const uint8_t* refs, const uint64_t* ref_off,
     const manta_ref_cuts_t* cuts)
 {
   if (!b) return MANTA_E_INVALID_ARG;
-  manta_ctx_t* ctx = b->ctx;
-  if (n_loci == 0 || !refs || !ref_off || !cuts) return fail(ctx, MANTA_E_INVALID_ARG, "manta_smallsv_upload_piles: null argument or empty batch");
-  int rc = checkPiles(ctx, piles, "manta_smallsv_upload_piles");
+  if (n_loci == 0 || !refs || !ref_off || !cuts) return fail(b->ctx, MANTA_E_INVALID_ARG, "manta_smallsv_upload_piles: null argument or empty batch");
+  const int rc = checkPiles(b->ctx, piles, "manta_smallsv_upload_piles");
   if (rc != MANTA_OK) return rc;
-  try {
-    rt::setDevice(ctx->deviceId);
-    rt::ScopedStream onStream(b->main);
-    b->uploaded = false;
-    b->refsOnCopy = false;
-    rc          = b->asmStage.plan(b->opt, n_loci, nullptr, piles->locus_read_begin, piles->read_len);
-    if (rc != MANTA_OK) return rc;
-    b->nLoci    = n_loci;
-    b->refBytes = ref_off[n_loci];
-    b->maxRef   = 0;
-    for (uint32_t l = 0; l < n_loci; ++l) {
-      if (ref_off[l + 1] < ref_off[l]) return fail(ctx, MANTA_E_INVALID_ARG, "manta_smallsv_upload_piles: ref_off not monotone");
-      b->maxRef = std::max<uint64_t>(b->maxRef, ref_off[l + 1] - ref_off[l]);
-      if (cuts[l].leading_cut < 0 || cuts[l].trailing_cut < 0 || cuts[l].max_leading_cut < 0 || cuts[l].max_trailing_cut < 0)
-        return fail(ctx, MANTA_E_INVALID_ARG, "manta_smallsv_upload_piles: negative reference cut");
-    }
-    uint8_t*  dRefs   = b->dRefs.as<uint8_t>(b->refBytes + 16);
-    uint64_t* dRefOff = b->dRefOff.as<uint64_t>(n_loci + 1);
-    auto*     dCuts   = b->dCuts.as<SmallSvCuts>(n_loci);
-    b->refsOnCopy     = b->streamUploads && !std::getenv("MANTA_AMD_NO_STREAM_UPLOAD");
-    if (b->refsOnCopy) {  // whole-batch call: piles chunk by chunk behind the running assembler, references behind them (manta_smallsv_upload)
-      b->asmStage.uploadPilesStreamed(*piles, b->copy);
-      rt::ScopedStream onCopy(b->copy);
-      rt::h2d(dRefs, refs, b->refBytes);
-      rt::h2d(dRefOff, ref_off, sizeof(uint64_t) * (n_loci + 1));
-      rt::h2d(dCuts, cuts, sizeof(SmallSvCuts) * n_loci);
-      b->refsReady.record();
-    } else {
-      b->asmStage.uploadPiles(*piles);
-      rt::h2d(dRefs, refs, b->refBytes);
-      rt::h2d(dRefOff, ref_off, sizeof(uint64_t) * (n_loci + 1));
-      rt::h2d(dCuts, cuts, sizeof(SmallSvCuts) * n_loci);
-      rt::sync();
-    }
-    b->uploaded = true;
-    return MANTA_OK;
-  } catch (const std::exception& e) {
-    return fail(ctx, MANTA_E_HIP, e.what());
-  }
+  // (a whole-batch call: piles chunk by chunk behind the running assembler, references behind them, as manta_smallsv_upload)
+  return pipeUpload(b, "manta_smallsv_upload_piles", n_loci, ReadsIn{nullptr, nullptr, piles->locus_read_begin, piles}, true, refs, ref_off, cuts);
 }
 
 }  // extern "C"
@@ -830,13 +926,7 @@ int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates)
     b->evAlign.record();
     uint32_t* hSmallPin = b->pSmall.as<uint32_t>(40);
     rt::d2hAsync(hSmallPin, dSmall, sizeof(uint32_t) * 40);
-    if (b->stageBehindRun) pipeStageEnqueue(b);  // the results start for the host behind the last kernel: no wake-up in between
-    if (earlyStage) {  // everything is queued and the aligners have ~2 ms to go: the host's share of the assembler's outputs
-      b->evEarlyStaged.sync();
-      as.finishEarly();
-      b->whileAligning();
-    }
-    rt::sync();
+    finishRun(b, earlyStage, alignOnly);
     std::memcpy(b->lastSmall, hSmallPin, sizeof(b->lastSmall));
     b->bucketHistory = true;
     if (fromHistory)
@@ -845,22 +935,13 @@ int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates)
           b->stats.n_align_launches++;
           b->stats.n_alignments += b->lastSmall[k];
         }
-    alignOnly.release();
-    if (as.chunks.active()) {  // all chunks were consumed by the kernel, so this returns at once; it closes the stream's error state
-      rt::ScopedStream onCopy(b->copy);
-      rt::sync();
-    }
     stage("aligned");
     b->qcRan = false;
     if (b->qcOn) {  // contig QC on the contigs, paths and windows where they are (manta_smallsv_set_qc); outside the timed stages
       smallsvQcLaunch(b);
       stage("qc");
     }
-    b->stats.assemble_ms = rt::elapsedMs(b->evStart, b->evAsm);
-    b->stats.schedule_ms = rt::elapsedMs(b->evAsm, b->evSched);
-    b->stats.align_ms    = rt::elapsedMs(b->evSched, b->evAlign);
-    b->stats.total_ms    = rt::elapsedMs(b->evStart, b->evAlign);
-    b->ran               = true;
+    b->ran = true;
     return MANTA_OK;
   } catch (const std::exception& e) {
     drainCopyStream(b);
@@ -872,36 +953,12 @@ extern "C" {
 
 int manta_smallsv_run(manta_smallsv_t* b) { return smallsvRunImpl(b, nullptr); }
 
-int manta_smallsv_stats(const manta_smallsv_t* b, manta_smallsv_stats_t* stats)
-{
-  if (!b || !stats) return MANTA_E_INVALID_ARG;
-  *stats = b->stats;
-  return MANTA_OK;
-}
+int manta_smallsv_stats(const manta_smallsv_t* b, manta_smallsv_stats_t* stats) { return pipeStats(b, stats); }
 
 int manta_smallsv_output_sizes(const manta_smallsv_t* b, uint64_t* contigs, uint64_t* seq_bytes, uint64_t* bits_words, uint64_t* cigar_words)
 {
-  if (!b || !contigs || !seq_bytes || !bits_words || !cigar_words) return MANTA_E_INVALID_ARG;
-  if (!b->ran) return fail(b->ctx, MANTA_E_INVALID_ARG, "manta_smallsv_output_sizes: run first");
-  try {
-    rt::setDevice(b->ctx->deviceId);  // the calling thread may have another device current (multi-GPU hosts)
-    rt::ScopedStream onStream(const_cast<manta_smallsv_t*>(b)->main);
-    b->asmStage.outputSizes(*contigs, *seq_bytes, *bits_words);
-    uint32_t hSmall[40];
-    rt::d2h(hSmall, b->dSmall.p, sizeof(hSmall));
-    uint64_t cig = 0;
-    std::memcpy(&cig, hSmall + 34, sizeof(uint64_t));
-    *cigar_words = cig + 64;
-    return MANTA_OK;
-  } catch (const std::exception& e) {
-    return fail(b->ctx, MANTA_E_HIP, e.what());
-  }
+  return pipeOutputSizes(b, contigs, seq_bytes, bits_words, cigar_words);
 }
-
-}  // extern "C"
-
-
-extern "C" {
 
 int manta_smallsv_download(
     manta_smallsv_t* b, manta_asm_locus_result_t* loci, manta_asm_contig_t* contigs, manta_smallsv_alignment_t* alignments,
@@ -909,20 +966,8 @@ int manta_smallsv_download(
     uint64_t bits_arena_cap, uint64_t* bits_arena_used, uint32_t* cigar_arena, uint64_t cigar_arena_cap,
     uint64_t* cigar_arena_used)
 {
-  if (!b) return MANTA_E_INVALID_ARG;
-  manta_ctx_t* ctx = b->ctx;
-  if (!b->ran) return fail(ctx, MANTA_E_INVALID_ARG, "manta_smallsv_download: run first");
-  if (!loci || !contigs || !alignments || !seq_arena || !bits_arena || !cigar_arena)
-    return fail(ctx, MANTA_E_INVALID_ARG, "manta_smallsv_download: null argument");
-  try {
-    rt::setDevice(ctx->deviceId);  // the calling thread may have another device current (multi-GPU hosts)
-    rt::ScopedStream onStream(b->main);
-    pipeStage(b);
-    return smallsvCompact(b, loci, contigs, alignments, 0, contigs_cap, seq_arena, seq_arena_cap, 0, seq_arena_used, bits_arena,
-                          bits_arena_cap, 0, bits_arena_used, cigar_arena, cigar_arena_cap, 0, cigar_arena_used);
-  } catch (const std::exception& e) {
-    return fail(ctx, MANTA_E_HIP, e.what());
-  }
+  return pipeDownload(b, loci, contigs, alignments, contigs_cap, seq_arena, seq_arena_cap, seq_arena_used, bits_arena, bits_arena_cap, bits_arena_used,
+                      cigar_arena, cigar_arena_cap, cigar_arena_used);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -958,55 +1003,9 @@ int manta_spanning_upload(
     const uint8_t* refs1, const uint64_t* ref1_off, const uint8_t* refs2, const uint64_t* ref2_off, const manta_jump_cuts_t* cuts)
 {
   if (!b) return MANTA_E_INVALID_ARG;
-  manta_ctx_t* ctx = b->ctx;
   if (n_loci == 0 || !bases || !read_off || !locus_read_begin || !refs1 || !ref1_off || !refs2 || !ref2_off || !cuts)
-    return fail(ctx, MANTA_E_INVALID_ARG, "manta_spanning_upload: null argument or empty batch");
-  try {
-    rt::setDevice(ctx->deviceId);  // the calling thread may have another device current (multi-GPU hosts)
-    rt::ScopedStream onStream(b->main);
-    b->uploaded = false;
-    int rc      = b->asmStage.plan(b->opt, n_loci, read_off, locus_read_begin);
-    if (rc != MANTA_OK) return rc;
-    b->nLoci     = n_loci;
-    b->ref1Bytes = ref1_off[n_loci];
-    b->ref2Bytes = ref2_off[n_loci];
-    for (uint32_t l = 0; l < n_loci; ++l) {
-      if (ref1_off[l + 1] < ref1_off[l] || ref2_off[l + 1] < ref2_off[l])
-        return fail(ctx, MANTA_E_INVALID_ARG, "manta_spanning_upload: reference offsets not monotone");
-      const manta_jump_cuts_t& c(cuts[l]);
-      if (c.align1_leading_cut < 0 || c.align1_trailing_cut < 0 || c.align2_leading_cut < 0 || c.align2_trailing_cut < 0)
-        return fail(ctx, MANTA_E_INVALID_ARG, "manta_spanning_upload: negative reference cut");
-    }
-    static_assert(sizeof(JumpCuts) == sizeof(manta_jump_cuts_t), "cuts layout");
-    uint8_t*  dRefs1   = b->dRefs1.as<uint8_t>(b->ref1Bytes + 16);
-    uint64_t* dRef1Off = b->dRef1Off.as<uint64_t>(n_loci + 1);
-    uint8_t*  dRefs2   = b->dRefs2.as<uint8_t>(b->ref2Bytes + 16);
-    uint64_t* dRef2Off = b->dRef2Off.as<uint64_t>(n_loci + 1);
-    JumpCuts* dCuts    = b->dCuts.as<JumpCuts>(n_loci);
-    auto      copyRefs = [&] {
-      rt::h2d(dRefs1, refs1, b->ref1Bytes);
-      rt::h2d(dRef1Off, ref1_off, sizeof(uint64_t) * (n_loci + 1));
-      rt::h2d(dRefs2, refs2, b->ref2Bytes);
-      rt::h2d(dRef2Off, ref2_off, sizeof(uint64_t) * (n_loci + 1));
-      rt::h2d(dCuts, cuts, sizeof(JumpCuts) * n_loci);
-    };
-    b->hostCuts.assign(reinterpret_cast<const JumpCuts*>(cuts), reinterpret_cast<const JumpCuts*>(cuts) + n_loci);
-    b->refsOnCopy = b->streamUploads && !std::getenv("MANTA_AMD_NO_STREAM_UPLOAD");
-    if (b->refsOnCopy) {  // whole-batch call: as manta_smallsv_upload -- bases in chunks behind the running assembler, references behind them
-      b->asmStage.uploadStreamed(bases, read_off, locus_read_begin, b->copy);
-      rt::ScopedStream onCopy(b->copy);
-      copyRefs();
-      b->refsReady.record();
-    } else {
-      b->asmStage.upload(bases, read_off, locus_read_begin);
-      copyRefs();
-      rt::sync();
-    }
-    b->uploaded = true;
-    return MANTA_OK;
-  } catch (const std::exception& e) {
-    return fail(ctx, MANTA_E_HIP, e.what());
-  }
+    return fail(b->ctx, MANTA_E_INVALID_ARG, "manta_spanning_upload: null argument or empty batch");
+  return pipeUpload(b, "manta_spanning_upload", n_loci, ReadsIn{bases, read_off, locus_read_begin, nullptr}, true, refs1, ref1_off, refs2, ref2_off, cuts);
 }
 
 int manta_spanning_upload_piles(
@@ -1014,41 +1013,13 @@ int manta_spanning_upload_piles(
     const uint8_t* refs2, const uint64_t* ref2_off, const manta_jump_cuts_t* cuts)
 {
   if (!b) return MANTA_E_INVALID_ARG;
-  manta_ctx_t* ctx = b->ctx;
   if (n_loci == 0 || !refs1 || !ref1_off || !refs2 || !ref2_off || !cuts)
-    return fail(ctx, MANTA_E_INVALID_ARG, "manta_spanning_upload_piles: null argument or empty batch");
-  int rc = checkPiles(ctx, piles, "manta_spanning_upload_piles");
+    return fail(b->ctx, MANTA_E_INVALID_ARG, "manta_spanning_upload_piles: null argument or empty batch");
+  const int rc = checkPiles(b->ctx, piles, "manta_spanning_upload_piles");
   if (rc != MANTA_OK) return rc;
-  try {
-    rt::setDevice(ctx->deviceId);
-    rt::ScopedStream onStream(b->main);
-    b->uploaded = false;
-    b->refsOnCopy = false;
-    rc          = b->asmStage.plan(b->opt, n_loci, nullptr, piles->locus_read_begin, piles->read_len);
-    if (rc != MANTA_OK) return rc;
-    b->asmStage.uploadPiles(*piles);
-    b->nLoci     = n_loci;
-    b->ref1Bytes = ref1_off[n_loci];
-    b->ref2Bytes = ref2_off[n_loci];
-    for (uint32_t l = 0; l < n_loci; ++l) {
-      if (ref1_off[l + 1] < ref1_off[l] || ref2_off[l + 1] < ref2_off[l])
-        return fail(ctx, MANTA_E_INVALID_ARG, "manta_spanning_upload_piles: reference offsets not monotone");
-      const manta_jump_cuts_t& c(cuts[l]);
-      if (c.align1_leading_cut < 0 || c.align1_trailing_cut < 0 || c.align2_leading_cut < 0 || c.align2_trailing_cut < 0)
-        return fail(ctx, MANTA_E_INVALID_ARG, "manta_spanning_upload_piles: negative reference cut");
-    }
-    rt::h2d(b->dRefs1.as<uint8_t>(b->ref1Bytes + 16), refs1, b->ref1Bytes);
-    rt::h2d(b->dRef1Off.as<uint64_t>(n_loci + 1), ref1_off, sizeof(uint64_t) * (n_loci + 1));
-    rt::h2d(b->dRefs2.as<uint8_t>(b->ref2Bytes + 16), refs2, b->ref2Bytes);
-    rt::h2d(b->dRef2Off.as<uint64_t>(n_loci + 1), ref2_off, sizeof(uint64_t) * (n_loci + 1));
-    rt::h2d(b->dCuts.as<JumpCuts>(n_loci), cuts, sizeof(JumpCuts) * n_loci);
-    b->hostCuts.assign(reinterpret_cast<const JumpCuts*>(cuts), reinterpret_cast<const JumpCuts*>(cuts) + n_loci);
-    rt::sync();
-    b->uploaded = true;
-    return MANTA_OK;
-  } catch (const std::exception& e) {
-    return fail(ctx, MANTA_E_HIP, e.what());
-  }
+  // (never streamed: the spanning pipeline has no chunked upload of piles)
+  return pipeUpload(b, "manta_spanning_upload_piles", n_loci, ReadsIn{nullptr, nullptr, piles->locus_read_begin, piles}, false, refs1, ref1_off, refs2,
+                    ref2_off, cuts);
 }
 
 }  // extern "C"
@@ -1313,24 +1284,9 @@ int spanningRunImpl(manta_spanning_t* b, StageGates* gates)
     alignPass(plainSides, maxWaves, "aligned round 1");
     launchPack(b, dTasks, dTasks2, dResults, dResults2, nullptr, dInfo, dCigar, cigarCap);
     b->evAlign.record();
-    if (b->stageBehindRun) pipeStageEnqueue(b);
-    if (earlyStage) {
-      b->evEarlyStaged.sync();
-      as.finishEarly();
-      b->whileAligning();
-    }
-    rt::sync();
-    alignOnly.release();
-    if (as.chunks.active()) {  // every chunk was consumed by the kernel, so this returns at once; it closes the copy stream's error state
-      rt::ScopedStream onCopy(b->copy);
-      rt::sync();
-    }
+    finishRun(b, earlyStage, alignOnly);
     stage("aligned round 2");
-    b->stats.assemble_ms = rt::elapsedMs(b->evStart, b->evAsm);
-    b->stats.schedule_ms = rt::elapsedMs(b->evAsm, b->evSched);
-    b->stats.align_ms    = rt::elapsedMs(b->evSched, b->evAlign);
-    b->stats.total_ms    = rt::elapsedMs(b->evStart, b->evAlign);
-    b->ran               = true;
+    b->ran = true;
     return MANTA_OK;
   } catch (const std::exception& e) {
     drainCopyStream(b);
@@ -1342,36 +1298,12 @@ extern "C" {
 
 int manta_spanning_run(manta_spanning_t* b) { return spanningRunImpl(b, nullptr); }
 
-int manta_spanning_stats(const manta_spanning_t* b, manta_smallsv_stats_t* stats)
-{
-  if (!b || !stats) return MANTA_E_INVALID_ARG;
-  *stats = b->stats;
-  return MANTA_OK;
-}
+int manta_spanning_stats(const manta_spanning_t* b, manta_smallsv_stats_t* stats) { return pipeStats(b, stats); }
 
 int manta_spanning_output_sizes(const manta_spanning_t* b, uint64_t* contigs, uint64_t* seq_bytes, uint64_t* bits_words, uint64_t* cigar_words)
 {
-  if (!b || !contigs || !seq_bytes || !bits_words || !cigar_words) return MANTA_E_INVALID_ARG;
-  if (!b->ran) return fail(b->ctx, MANTA_E_INVALID_ARG, "manta_spanning_output_sizes: run first");
-  try {
-    rt::setDevice(b->ctx->deviceId);  // the calling thread may have another device current (multi-GPU hosts)
-    rt::ScopedStream onStream(const_cast<manta_spanning_t*>(b)->main);
-    b->asmStage.outputSizes(*contigs, *seq_bytes, *bits_words);
-    uint32_t hSmall[72];
-    rt::d2h(hSmall, b->dSmall.p, sizeof(hSmall));
-    uint64_t cig = 0;
-    std::memcpy(&cig, hSmall + 64, sizeof(uint64_t));
-    *cigar_words = cig + 64;
-    return MANTA_OK;
-  } catch (const std::exception& e) {
-    return fail(b->ctx, MANTA_E_HIP, e.what());
-  }
+  return pipeOutputSizes(b, contigs, seq_bytes, bits_words, cigar_words);
 }
-
-}  // extern "C"
-
-
-extern "C" {
 
 int manta_spanning_download(
     manta_spanning_t* b, manta_asm_locus_result_t* loci, manta_asm_contig_t* contigs, manta_spanning_alignment_t* alignments,
@@ -1379,25 +1311,11 @@ int manta_spanning_download(
     uint64_t bits_arena_cap, uint64_t* bits_arena_used, uint32_t* cigar_arena, uint64_t cigar_arena_cap,
     uint64_t* cigar_arena_used)
 {
-  if (!b) return MANTA_E_INVALID_ARG;
-  manta_ctx_t* ctx = b->ctx;
-  if (!b->ran) return fail(ctx, MANTA_E_INVALID_ARG, "manta_spanning_download: run first");
-  if (!loci || !contigs || !alignments || !seq_arena || !bits_arena || !cigar_arena)
-    return fail(ctx, MANTA_E_INVALID_ARG, "manta_spanning_download: null argument");
-  try {
-    rt::setDevice(ctx->deviceId);  // the calling thread may have another device current (multi-GPU hosts)
-    rt::ScopedStream onStream(b->main);
-    pipeStage(b);
-    return spanningCompact(b, loci, contigs, alignments, 0, contigs_cap, seq_arena, seq_arena_cap, 0, seq_arena_used, bits_arena,
-                           bits_arena_cap, 0, bits_arena_used, cigar_arena, cigar_arena_cap, 0, cigar_arena_used);
-  } catch (const std::exception& e) {
-    return fail(ctx, MANTA_E_HIP, e.what());
-  }
+  return pipeDownload(b, loci, contigs, alignments, contigs_cap, seq_arena, seq_arena_cap, seq_arena_used, bits_arena, bits_arena_cap, bits_arena_used,
+                      cigar_arena, cigar_arena_cap, cigar_arena_used);
 }
 
 }  // extern "C"
-
-
 
 manta_ctx::~manta_ctx()
 {

@@ -1597,18 +1597,18 @@ struct AsmStage {
 };
 
 }  // namespace manta_host
-using namespace manta_host;
 
-struct manta_smallsv {
+/// What the two fused pipelines share: the assembler stage, the streams and events of a run, the upload's state, the device -> host
+/// staging of the packed results and what a whole-batch worker keeps on its pipeline.  Plain data; manta_smallsv / manta_spanning add
+/// their reference buffers, their aligners' state and their extra score.
+struct PipeBase {
   manta_ctx_t*          ctx;
   AsmStage              asmStage;
   manta_asm_options_t   opt{};
   manta_align_scores_t  scores{};
-  int32_t               largeIndel = 0;
-  uint32_t              nLoci      = 0;
-  uint64_t              refBytes = 0, maxRef = 0;
+  uint32_t              nLoci = 0;
   bool                  uploaded = false, ran = false;
-  DevBuf                dRefs, dRefOff, dCuts, dTasks, dInfo, dResults, dBucketIds, dBucketIds2, dSmall, dCigar, dTable, dPtrWs;
+  DevBuf                dCuts, dTasks, dInfo, dResults, dBucketIds, dBucketIds2, dSmall, dCigar, dPtrWs;
   rt::Event             evStart, evAsm, evSched, evAlign, refsReady;
   rt::Stream            main;  // everything of this pipeline except the aligner buckets
   rt::Stream            copy;  // streamed upload of the read bases (whole-batch calls)
@@ -1624,9 +1624,6 @@ struct manta_smallsv {
   uint32_t*             hCig    = nullptr;
   uint32_t*             hPackCnt = nullptr;  // [0] packed contigs, [1] packed cigar words
   uint64_t              packLast[2] = {0, 0}, packedCopied = 0, cigCopied = 0;  // speculative staging (pipeStageEnqueue)
-  PinnedBuf             pSmall;
-  uint32_t              lastSmall[40] = {0};  // bucket counters of the previous run (grids of the next one)
-  bool                  bucketHistory = false;
   bool                  stageBehindRun = false;  // whole-batch calls: the run queues the staging behind its last kernel
   bool                  staged = false;
   // whole-batch calls: the host's work on the assembler's outputs (sizes, compaction into the caller's arrays) while the aligners run.
@@ -1635,35 +1632,36 @@ struct manta_smallsv {
   std::function<void()> whileAligning;
   rt::Event             evEarlyStaged;
   PinnedBuf             hostOff[3], hostBegin;  // whole-batch worker: a block's rebased offset arrays (api_batch.cpp: rebase), kept across calls
+  explicit PipeBase(manta_ctx_t* c) : ctx(c), asmStage(c) {}
+};
+
+struct manta_smallsv : PipeBase {
+  using Alignment = manta_smallsv_alignment_t;
+  static constexpr const char* kFamily        = "smallsv";
+  static constexpr int         kCigarUsedWord = 34;    // of dSmall (smallsvRunImpl)
+  static constexpr bool        kEarlyStream   = true;  // a streamed upload of read bases starts its DMA before plan() (AsmStage::startStream)
+  int32_t               largeIndel = 0;
+  uint64_t              refBytes = 0, maxRef = 0;
+  DevBuf                dRefs, dRefOff, dTable;
+  PinnedBuf             pSmall;
+  uint32_t              lastSmall[40] = {0};  // bucket counters of the previous run (grids of the next one)
+  bool                  bucketHistory = false;
   // contig QC behind the aligners (manta_smallsv_set_qc; off unless asked for)
   bool                  qcOn = false, qcRan = false;
   manta_align_scores_t  qcScores{};
   uint32_t              qcMinIndel = 0;
   DevBuf                dQc, dQcSegs, dQcCnt;
-  explicit manta_smallsv(manta_ctx_t* c) : ctx(c), asmStage(c) {}
+  using PipeBase::PipeBase;
 };
 
-
-struct manta_spanning {
-  manta_ctx_t*          ctx;
-  AsmStage              asmStage;
-  manta_asm_options_t   opt{};
-  manta_align_scores_t  scores{};
+struct manta_spanning : PipeBase {
+  using Alignment = manta_spanning_alignment_t;
+  static constexpr const char* kFamily        = "spanning";
+  static constexpr int         kCigarUsedWord = 64;  // of dSmall (spanningRunImpl)
+  static constexpr bool        kEarlyStream   = false;
   int32_t               jumpScore = 0;
-  uint32_t              nLoci     = 0;
   uint64_t              ref1Bytes = 0, ref2Bytes = 0;
-  bool                  uploaded = false, ran = false;
-  DevBuf                dRefs1, dRef1Off, dRefs2, dRef2Off, dCuts, dTasks, dTasks2, dInfo, dResults, dResults2, dBucketIds, dBucketIds2, dSmall,
-      dCigar, dPtrWs;
-  rt::Event             evStart, evAsm, evSched, evAlign, refsReady;
-  rt::Stream            main;
-  rt::Stream            copy;  // streamed upload of the read bases (whole-batch calls)
-  bool                  streamUploads = false, refsOnCopy = false;
-  rt::Stream            side[3];
-  rt::Event             sideDone[3];
-  manta_smallsv_stats_t stats{};
-  DevBuf                dFirst, dPacked, dCigPacked, dPackCnt;
-  PinnedBuf             pFirst, pPacked, pCig, pPackCnt;
+  DevBuf                dRefs1, dRef1Off, dRefs2, dRef2Off, dTasks2, dResults2;
   // the early alignment pass (spanningRunImpl): the contigs of the loci that are final after the first word length are aligned while the
   // word-length rounds of the tandem piles still run on `main`
   // (`early` is a CU-masked stream like its side streams: the runtime multiplexes ordinary streams onto a few hardware queues -- the first
@@ -1675,25 +1673,34 @@ struct manta_spanning {
   DevBuf                dPassMask;
   uint32_t              earlyLoci = 0;      // loci the last run aligned early
   std::vector<JumpCuts> hostCuts;  // the caller's cuts of the uploaded batch
-  uint32_t*             hFirst  = nullptr;
-  PackedContigOut*      hPacked = nullptr;
-  uint32_t*             hCig    = nullptr;
-  uint32_t*             hPackCnt = nullptr;
-  uint64_t              packLast[2] = {0, 0}, packedCopied = 0, cigCopied = 0;
-  bool                  stageBehindRun = false;
-  bool                  staged = false;
-  std::function<void()> whileAligning;  // as manta_smallsv::whileAligning (called while the last alignment pass runs)
-  rt::Event             evEarlyStaged;
-  PinnedBuf             hostOff[3], hostBegin;  // whole-batch worker: a block's rebased offset arrays, kept across calls
-  explicit manta_spanning(manta_ctx_t* c) : ctx(c), asmStage(c) {}
+  using PipeBase::PipeBase;
 };
+
+/// Stage gates of a whole-batch call with several workers: at most one block assembles and at most one block
+/// aligns at any time, so that block B's (memory-bound) assembler overlaps block A's (VALU-bound) aligners and transfers
+/// instead of two persistent assemblers fighting for the same wave slots.
+/// assembler waves per CU while another block's aligners share the device: 3 of the 4 wave slots per SIMD (128 VGPRs each)
+static const int kPipelinedAsmWavesPerCu = std::getenv("MANTA_AMD_PIPELINED_ASM_WAVES") ? std::atoi(std::getenv("MANTA_AMD_PIPELINED_ASM_WAVES")) : 12;
+struct StageGates {
+  std::mutex asmMu, alignMu;
+};
+inline std::mutex g_streamedAsmMuOfDevice[16];  // see smallsvRunImpl; one per device (id modulo 16)
+inline std::mutex& streamedAsmMu(const manta_ctx_t* ctx) { return g_streamedAsmMuOfDevice[unsigned(ctx->deviceId) % 16u]; }
+struct GateLock {
+  std::unique_lock<std::mutex> l;
+  GateLock(StageGates* g, std::mutex StageGates::*m) { if (g) l = std::unique_lock<std::mutex>(g->*m); }
+  void release() { if (l.owns_lock()) l.unlock(); }
+};
+
+/// one run of a fused pipeline (api.cpp); `gates` = the stage gates of a whole-batch call with several workers, else nullptr
+int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates);
+int spanningRunImpl(manta_spanning_t* b, StageGates* gates);
 
 namespace manta_host {
 
 /// the last kernel of a pipeline run: dense per-contig records + back-to-back CIGARs (pack_results_kernel)
-template <typename Pipe>
-void launchPack(Pipe* b, const AlignTaskDev* tasks, const AlignTaskDev* tasks2, const AlignResultDev* res, const AlignResultDev* res2,
-                const SmallSvTaskInfo* infoSmall, const SpanTaskInfo* infoSpan, const uint32_t* cigar, uint64_t cigarCap)
+inline void launchPack(PipeBase* b, const AlignTaskDev* tasks, const AlignTaskDev* tasks2, const AlignResultDev* res, const AlignResultDev* res2,
+                       const SmallSvTaskInfo* infoSmall, const SpanTaskInfo* infoSpan, const uint32_t* cigar, uint64_t cigarCap)
 {
   const uint32_t nLoci  = b->nLoci;
   const uint64_t nSlots = uint64_t(nLoci) * b->opt.max_assembly_count;
@@ -1709,18 +1716,13 @@ void launchPack(Pipe* b, const AlignTaskDev* tasks, const AlignTaskDev* tasks2, 
   K.info_small         = infoSmall;
   K.info_span          = infoSpan;
   K.cigar              = cigar;
-  K.first              = b->dFirst.template as<uint32_t>(nLoci);
-  K.packed             = b->dPacked.template as<PackedContigOut>(nSlots);
-  K.cigar_packed       = b->dCigPacked.template as<uint32_t>(cigarCap + 16);
-  K.counters           = b->dPackCnt.template as<uint32_t>(4);
+  K.first              = b->dFirst.as<uint32_t>(nLoci);
+  K.packed             = b->dPacked.as<PackedContigOut>(nSlots);
+  K.cigar_packed       = b->dCigPacked.as<uint32_t>(cigarCap + 16);
+  K.counters           = b->dPackCnt.as<uint32_t>(4);
   rt::dzero(K.counters, 16);
   rt::launch(pack_results_kernel, rt::roundGrid(int(std::min<uint64_t>((nLoci + 63) / 64, uint64_t(std::max(1, b->ctx->cuCount * 8))))), 0, K);
 }
-
-}  // namespace manta_host
-using namespace manta_host;
-
-namespace manta_host {
 
 inline void qcSetScores(QcParams& Q, const manta_align_scores_t& sc, uint32_t minIndel)
 {
@@ -1819,46 +1821,29 @@ inline int checkPiles(manta_ctx_t* ctx, const manta_packed_piles_t* pl, const ch
     return fail(ctx, MANTA_E_INVALID_ARG, std::string(who) + ": null pointer in the packed piles");
   return MANTA_OK;
 }
-}  // namespace manta_host
-using namespace manta_host;
 
-/// Stage gates of a whole-batch call with several workers: at most one block assembles and at most one block
-/// aligns at any time, so that block B's (memory-bound) assembler overlaps block A's (VALU-bound) aligners and transfers
-/// instead of two persistent assemblers fighting for the same wave slots.
-/// assembler waves per CU while another block's aligners share the device: 3 of the 4 wave slots per SIMD (128 VGPRs each)
-static const int kPipelinedAsmWavesPerCu = std::getenv("MANTA_AMD_PIPELINED_ASM_WAVES") ? std::atoi(std::getenv("MANTA_AMD_PIPELINED_ASM_WAVES")) : 12;
-struct StageGates {
-  std::mutex asmMu, alignMu;
-};
-inline std::mutex g_streamedAsmMuOfDevice[16];  // see smallsvRunImpl; one per device (id modulo 16)
-inline std::mutex& streamedAsmMu(const manta_ctx_t* ctx) { return g_streamedAsmMuOfDevice[unsigned(ctx->deviceId) % 16u]; }
-struct GateLock {
-  std::unique_lock<std::mutex> l;
-  GateLock(StageGates* g, std::mutex StageGates::*m) { if (g) l = std::unique_lock<std::mutex>(g->*m); }
-  void release() { if (l.owns_lock()) l.unlock(); }
+/// the reads of an upload or of a whole-batch call: read bases with their offsets, or packed piles (`piles` != nullptr; `locus_read_begin`
+/// is the piles' own then)
+struct ReadsIn {
+  const uint8_t*              bases;
+  const uint64_t*             read_off;
+  const uint32_t*             locus_read_begin;
+  const manta_packed_piles_t* piles;
 };
 
-/// failure exit of a pipeline run: let queued DMA reads of the caller's buffers (streamed upload) finish before the call returns
-template <typename Pipe>
-void drainCopyStream(Pipe* b) noexcept
+/// failure exit of an upload or a pipeline run: let queued DMA reads of the caller's buffers (streamed upload) finish before the call returns
+inline void drainCopyStream(PipeBase* b) noexcept
 {
   ChunkStream::drain(&b->copy);
 }
 
-/// one run of a fused pipeline (api.cpp); `gates` = the stage gates of a whole-batch call with several workers, else nullptr
-int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates);
-int spanningRunImpl(manta_spanning_t* b, StageGates* gates);
-
-namespace manta_host {
-
 /// device -> pinned staging of one finished pipeline run (both pipelines): counters + locus records + first-contig
 /// index in the first round trip, then exactly the used part of every arena
-template <typename Pipe>
-void pipeStageEnqueue(Pipe* b)
+inline void pipeStageEnqueue(PipeBase* b)
 {
   const uint32_t nLoci = b->nLoci;
-  b->hPackCnt          = b->pPackCnt.template as<uint32_t>(4);
-  b->hFirst            = b->pFirst.template as<uint32_t>(nLoci);
+  b->hPackCnt          = b->pPackCnt.as<uint32_t>(4);
+  b->hFirst            = b->pFirst.as<uint32_t>(nLoci);
   auto packCopies = [&] {
         rt::d2hAsync(b->hPackCnt, b->dPackCnt.p, 16);
         rt::d2hAsync(b->hFirst, b->dFirst.p, sizeof(uint32_t) * nLoci);
@@ -1867,8 +1852,8 @@ void pipeStageEnqueue(Pipe* b)
         b->cigCopied    = b->packLast[1] + b->packLast[1] / 4 + (b->packLast[1] ? 1024 : 0);
         b->packedCopied = std::min<uint64_t>(b->packedCopied, b->dPacked.cap / sizeof(PackedContigOut));
         b->cigCopied    = std::min<uint64_t>(b->cigCopied, b->dCigPacked.cap / sizeof(uint32_t));
-        b->hPacked      = b->pPacked.template as<PackedContigOut>(b->packedCopied + 1);
-        b->hCig         = b->pCig.template as<uint32_t>(b->cigCopied + 1);
+        b->hPacked      = b->pPacked.as<PackedContigOut>(b->packedCopied + 1);
+        b->hCig         = b->pCig.as<uint32_t>(b->cigCopied + 1);
         rt::d2hAsync(b->hPacked, b->dPacked.p, sizeof(PackedContigOut) * b->packedCopied);
         rt::d2hAsync(b->hCig, b->dCigPacked.p, sizeof(uint32_t) * b->cigCopied);
       };
@@ -1877,21 +1862,20 @@ void pipeStageEnqueue(Pipe* b)
   else
     b->asmStage.stageEnqueue(packCopies, false);
 }
-template <typename Pipe>
-void pipeStageFinish(Pipe* b)
+inline void pipeStageFinish(PipeBase* b)
 {
   b->asmStage.stageFinish([&](bool& queued) {
     const uint64_t nP = b->hPackCnt[0], nG = b->hPackCnt[1];
     b->packLast[0] = nP;
     b->packLast[1] = nG;
     if (nP > b->packedCopied) {
-      b->hPacked = b->pPacked.template as<PackedContigOut>(nP + 1, true);
+      b->hPacked = b->pPacked.as<PackedContigOut>(nP + 1, true);
       rt::d2hAsync(b->hPacked + b->packedCopied, static_cast<const PackedContigOut*>(b->dPacked.p) + b->packedCopied,
                    sizeof(PackedContigOut) * (nP - b->packedCopied));
       queued = true;
     }
     if (nG > b->cigCopied) {
-      b->hCig = b->pCig.template as<uint32_t>(nG + 1, true);
+      b->hCig = b->pCig.as<uint32_t>(nG + 1, true);
       rt::d2hAsync(b->hCig + b->cigCopied, static_cast<const uint32_t*>(b->dCigPacked.p) + b->cigCopied, sizeof(uint32_t) * (nG - b->cigCopied));
       queued = true;
     }
@@ -1900,8 +1884,7 @@ void pipeStageFinish(Pipe* b)
 }
 /// device -> pinned staging of one finished pipeline run (both pipelines).  A run that queued the staging behind its last
 /// kernel (stageBehindRun) has done the first half already.
-template <typename Pipe>
-void pipeStage(Pipe* b)
+inline void pipeStage(PipeBase* b)
 {
   if (!b->asmStage.stageQueued) {
     pipeStageEnqueue(b);
@@ -1910,46 +1893,78 @@ void pipeStage(Pipe* b)
   pipeStageFinish(b);
 }
 
-template <typename Pipe>
 struct PackedContigs {
-  const Pipe* b;
+  const PipeBase* b;
   const AsmContigOut& operator()(uint32_t l, uint32_t c) const { return b->hPacked[b->hFirst[l] + c].contig; }
 };
 
 /// bytes a pipeStage moved over PCIe (for the batch statistics)
-template <typename Pipe>
-uint64_t pipeStagedBytes(const Pipe* b)
+inline uint64_t pipeStagedBytes(const PipeBase* b)
 {
   return b->asmStage.seqUsedDev + 8 * b->asmStage.bitsUsedDev + (sizeof(AsmLocusOut) + 4) * uint64_t(b->nLoci) +
          sizeof(PackedContigOut) * uint64_t(b->hPackCnt[0]) + 4ull * b->hPackCnt[1] + 128 + 16;
 }
 
-/// staging -> caller records/arenas.  `loci` is this block's slice; `contigs` / `alignments` are the caller's whole arrays
-/// and this block writes [contigBase, contigBase + contigs_cap); the three arenas are this block's regions, offsets in the
-/// records are made relative to the caller's arena starts by adding the *Base values.
-inline int smallsvCompactAlign(
-    manta_smallsv* b, const manta_asm_locus_result_t* loci, manta_smallsv_alignment_t* alignments, uint32_t* cigar_arena, uint64_t cigar_arena_cap,
-    uint64_t cigarBase, uint64_t* cigar_arena_used, uint32_t lBegin, uint32_t lEnd, uint64_t* cellsOut, uint64_t* ptrBytesOut, int worst);
-inline int smallsvCompact(
-    manta_smallsv* b, manta_asm_locus_result_t* loci, manta_asm_contig_t* contigs, manta_smallsv_alignment_t* alignments,
-    uint64_t contigBase, uint64_t contigs_cap, uint8_t* seq_arena, uint64_t seq_arena_cap, uint64_t seqBase, uint64_t* seq_arena_used,
-    uint64_t* bits_arena, uint64_t bits_arena_cap, uint64_t bitsBase, uint64_t* bits_arena_used, uint32_t* cigar_arena,
-    uint64_t cigar_arena_cap, uint64_t cigarBase, uint64_t* cigar_arena_used, uint32_t lBegin = 0, uint32_t lEnd = ~0u,
-    uint64_t* cellsOut = nullptr, uint64_t* ptrBytesOut = nullptr)
+/// ---- staging -> the caller's alignment records: what differs between the pipelines ----
+/// alignmentRecord(b, l, c, h, cigarOff, a, ptrBytes): the record `a` (zeroed by the caller) of contig c of locus l from its packed record h;
+/// returns the CIGAR words the record refers to -- they start at h.cigar_off of the staging and go to `cigarOff` of the caller's arena.  A
+/// contig without an alignment gets its status (a->align.status != MANTA_OK) and nothing else; `a` == nullptr: only the count.  An overload
+/// per pipeline, resolved where compactAlign / cigarWords are instantiated: no indirect call in the per-contig loops.
+inline bool packedAligned(const PackedContigOut& h) { return h.info_status == 0 && h.bucket >= 0 && h.res_status == 0; }
+
+inline uint64_t alignmentRecord(const manta_smallsv*, uint32_t l, uint32_t c, const PackedContigOut& h, uint64_t cigarOff, manta_smallsv_alignment_t* a,
+                                uint64_t* ptrBytes)
 {
-  // [lBegin, lEnd): the loci of this call (a whole-batch call compacts a block in a few ranges, one host thread each); every
-  // output pointer / base is that of the range's first record
-  lEnd   = std::min(lEnd, b->nLoci);
-  int rc = b->asmStage.compact(PackedContigs<manta_smallsv>{b}, loci, contigs + contigBase, contigs_cap, seq_arena, seq_arena_cap, seq_arena_used,
-                               bits_arena, bits_arena_cap, bits_arena_used, contigBase, seqBase, bitsBase, lBegin, lEnd);
-  if (rc != MANTA_OK && !perItemCode(rc)) return rc;
-  return smallsvCompactAlign(b, loci, alignments, cigar_arena, cigar_arena_cap, cigarBase, cigar_arena_used, lBegin, lEnd, cellsOut, ptrBytesOut, rc);
+  const uint64_t n = h.cigar1_len;
+  if (!a) return n;
+  a->adjusted_leading_cut  = h.a;
+  a->adjusted_trailing_cut = h.b;
+  if (!packedAligned(h)) {
+    a->align.status = (h.info_status == 5) ? MANTA_E_DEVICE_FAULT : MANTA_E_UNSUPPORTED;
+    if (std::getenv("MANTA_AMD_DEBUG") || std::getenv("MANTA_AMD_DEBUG_STATUS"))
+      std::fprintf(stderr, "manta_amd: locus %u contig %u schedule status %d bucket %d align status %d\n", l, c, h.info_status, h.bucket, h.res_status);
+    return 0;
+  }
+  a->align.score      = h.score;
+  a->align.is_jumped  = h.is_jumped;
+  a->align.begin_pos1 = h.begin1 + h.a;  // SVCandidateAssemblyRefiner.cpp:2039
+  a->align.cigar1_len = h.cigar1_len;
+  a->align.cigar1_off = cigarOff;
+  a->align.cigar2_off = cigarOff + n;
+  *ptrBytes += 2ull * (uint64_t(h.query_len) + 1) * (uint64_t(h.ref_len) + 1);
+  return n;
 }
-/// the second half of smallsvCompact: the alignment records and CIGARs of the loci [lBegin, lEnd), whose locus records (first_contig,
+
+inline uint64_t alignmentRecord(const manta_spanning* b, uint32_t l, uint32_t, const PackedContigOut& h, uint64_t cigarOff, manta_spanning_alignment_t* a,
+                                uint64_t* ptrBytes)
+{
+  const uint64_t n = uint64_t(h.cigar1_len) + h.cigar2_len;
+  if (!a) return n;
+  const bool uncut = h.a != 0;
+  a->is_uncut      = uncut ? 1 : 0;
+  if (!packedAligned(h)) {
+    a->align.status = (h.info_status == 5) ? MANTA_E_DEVICE_FAULT : (h.info_status == 6) ? MANTA_E_EMPTY_SEQ : MANTA_E_UNSUPPORTED;
+    return 0;
+  }
+  a->align.score            = h.score;
+  a->align.is_jumped        = h.is_jumped;
+  a->align.begin_pos1       = h.begin1 + (uncut ? 0 : b->hostCuts[l].a1Lead);  // SVCandidateAssemblyRefiner.cpp:1716-1717
+  a->align.begin_pos2       = h.begin2 + (uncut ? 0 : b->hostCuts[l].a2Lead);
+  a->align.jump_insert_size = h.jump_insert_size;
+  a->align.jump_range       = h.jump_range;
+  a->align.cigar1_len       = h.cigar1_len;
+  a->align.cigar2_len       = h.cigar2_len;
+  a->align.cigar1_off       = cigarOff;
+  a->align.cigar2_off       = cigarOff + h.cigar1_len;
+  *ptrBytes += (uint64_t(h.query_len) + 1) * (uint64_t(h.ref_len) + 2);
+  return n;
+}
+
+/// the second half of compact(): the alignment records and CIGARs of the loci [lBegin, lEnd), whose locus records (first_contig,
 /// n_contigs) AsmStage::compact has written; `worst`: what that call returned (a per-item code or MANTA_OK)
-inline int smallsvCompactAlign(
-    manta_smallsv* b, const manta_asm_locus_result_t* loci, manta_smallsv_alignment_t* alignments, uint32_t* cigar_arena, uint64_t cigar_arena_cap,
-    uint64_t cigarBase, uint64_t* cigar_arena_used, uint32_t lBegin, uint32_t lEnd, uint64_t* cellsOut, uint64_t* ptrBytesOut, int worst)
+template <typename Pipe>
+int compactAlign(Pipe* b, const manta_asm_locus_result_t* loci, typename Pipe::Alignment* alignments, uint32_t* cigar_arena, uint64_t cigar_arena_cap,
+                 uint64_t cigarBase, uint64_t* cigar_arena_used, uint32_t lBegin, uint32_t lEnd, uint64_t* cellsOut, uint64_t* ptrBytesOut, int worst)
 {
   manta_ctx_t* ctx = b->ctx;
   lEnd             = std::min(lEnd, b->nLoci);
@@ -1957,30 +1972,18 @@ inline int smallsvCompactAlign(
   for (uint32_t l = lBegin; l < lEnd; ++l) {
     if (loci[l].status != MANTA_OK) continue;
     for (uint32_t c = 0; c < loci[l].n_contigs; ++c) {
-      manta_smallsv_alignment_t& a(alignments[loci[l].first_contig + c]);
+      typename Pipe::Alignment& a(alignments[loci[l].first_contig + c]);
       std::memset(&a, 0, sizeof(a));
       const PackedContigOut& h(b->hPacked[b->hFirst[l] + c]);
-      a.adjusted_leading_cut  = h.a;
-      a.adjusted_trailing_cut = h.b;
-      if (h.info_status != 0 || h.bucket < 0 || h.res_status != 0) {
-        a.align.status = (h.info_status == 5) ? MANTA_E_DEVICE_FAULT : MANTA_E_UNSUPPORTED;
-        worst          = a.align.status;
-        if (std::getenv("MANTA_AMD_DEBUG") || std::getenv("MANTA_AMD_DEBUG_STATUS"))
-          std::fprintf(stderr, "manta_amd: locus %u contig %u schedule status %d bucket %d align status %d\n", l, c, h.info_status, h.bucket, h.res_status);
+      const uint64_t         n = alignmentRecord(b, l, c, h, cigarBase + used, &a, &ptrBytes);
+      if (a.align.status != MANTA_OK) {
+        worst = a.align.status;
         continue;
       }
-      const uint64_t n = h.cigar1_len;
-      if (used + n > cigar_arena_cap) return fail(ctx, MANTA_E_CAPACITY, "manta_smallsv_download: cigar arena too small");
+      if (used + n > cigar_arena_cap) return fail(ctx, MANTA_E_CAPACITY, std::string("manta_") + Pipe::kFamily + "_download: cigar arena too small");
       std::memcpy(cigar_arena + used, b->hCig + h.cigar_off, sizeof(uint32_t) * n);
-      a.align.score      = h.score;
-      a.align.is_jumped  = h.is_jumped;
-      a.align.begin_pos1 = h.begin1 + h.a;  // SVCandidateAssemblyRefiner.cpp:2039
-      a.align.cigar1_len = h.cigar1_len;
-      a.align.cigar1_off = cigarBase + used;
-      a.align.cigar2_off = cigarBase + used + n;
       used += n;
       cells += uint64_t(h.query_len) * h.ref_len;
-      ptrBytes += 2ull * (uint64_t(h.query_len) + 1) * (uint64_t(h.ref_len) + 1);
     }
   }
   if (cellsOut) {  // ranged call: the caller adds the ranges up
@@ -1991,100 +1994,31 @@ inline int smallsvCompactAlign(
     b->stats.ptr_matrix_bytes = ptrBytes;
   }
   if (cigar_arena_used) *cigar_arena_used = used;
-  if (worst != MANTA_OK) return fail(ctx, worst, "manta_smallsv_download: one or more loci/contigs failed; see per-item status");
+  if (worst != MANTA_OK) return fail(ctx, worst, std::string("manta_") + Pipe::kFamily + "_download: one or more loci/contigs failed; see per-item status");
   return MANTA_OK;
 }
 
-/// CIGAR words smallsvCompact writes for the loci [lBegin, lEnd)
-inline uint64_t smallsvCigarWords(const manta_smallsv* b, uint32_t lBegin, uint32_t lEnd)
+/// staging -> caller records/arenas.  `loci` is this block's slice; `contigs` / `alignments` are the caller's whole arrays
+/// and this block writes [contigBase, contigBase + contigs_cap); the three arenas are this block's regions, offsets in the
+/// records are made relative to the caller's arena starts by adding the *Base values.
+template <typename Pipe>
+int compact(Pipe* b, manta_asm_locus_result_t* loci, manta_asm_contig_t* contigs, typename Pipe::Alignment* alignments, uint64_t contigBase,
+            uint64_t contigs_cap, uint8_t* seq_arena, uint64_t seq_arena_cap, uint64_t seqBase, uint64_t* seq_arena_used, uint64_t* bits_arena,
+            uint64_t bits_arena_cap, uint64_t bitsBase, uint64_t* bits_arena_used, uint32_t* cigar_arena, uint64_t cigar_arena_cap, uint64_t cigarBase,
+            uint64_t* cigar_arena_used, uint32_t lBegin = 0, uint32_t lEnd = ~0u, uint64_t* cellsOut = nullptr, uint64_t* ptrBytesOut = nullptr)
 {
-  uint64_t n = 0;
-  for (uint32_t l = lBegin; l < lEnd; ++l) {
-    const AsmLocusOut& h(b->asmStage.hLoci[l]);
-    if (h.status != ASM_OK) continue;
-    for (uint32_t c = 0; c < h.n_contigs; ++c) {
-      const PackedContigOut& pc(b->hPacked[b->hFirst[l] + c]);
-      if (pc.info_status == 0 && pc.bucket >= 0 && pc.res_status == 0) n += pc.cigar1_len;
-    }
-  }
-  return n;
-}
-
-}  // namespace manta_host
-using namespace manta_host;
-
-namespace manta_host {
-
-inline int spanningCompactAlign(
-    manta_spanning* b, const manta_asm_locus_result_t* loci, manta_spanning_alignment_t* alignments, uint32_t* cigar_arena, uint64_t cigar_arena_cap,
-    uint64_t cigarBase, uint64_t* cigar_arena_used, uint32_t lBegin, uint32_t lEnd, uint64_t* cellsOut, uint64_t* ptrBytesOut, int worst);
-inline int spanningCompact(
-    manta_spanning* b, manta_asm_locus_result_t* loci, manta_asm_contig_t* contigs, manta_spanning_alignment_t* alignments,
-    uint64_t contigBase, uint64_t contigs_cap, uint8_t* seq_arena, uint64_t seq_arena_cap, uint64_t seqBase, uint64_t* seq_arena_used,
-    uint64_t* bits_arena, uint64_t bits_arena_cap, uint64_t bitsBase, uint64_t* bits_arena_used, uint32_t* cigar_arena,
-    uint64_t cigar_arena_cap, uint64_t cigarBase, uint64_t* cigar_arena_used, uint32_t lBegin = 0, uint32_t lEnd = ~0u,
-    uint64_t* cellsOut = nullptr, uint64_t* ptrBytesOut = nullptr)
-{
-  // [lBegin, lEnd) and the *Out totals: as smallsvCompact
+  // [lBegin, lEnd): the loci of this call (a whole-batch call compacts a block in a few ranges, one host thread each); every
+  // output pointer / base is that of the range's first record
   lEnd   = std::min(lEnd, b->nLoci);
-  int rc = b->asmStage.compact(PackedContigs<manta_spanning>{b}, loci, contigs + contigBase, contigs_cap, seq_arena, seq_arena_cap, seq_arena_used,
-                               bits_arena, bits_arena_cap, bits_arena_used, contigBase, seqBase, bitsBase, lBegin, lEnd);
+  int rc = b->asmStage.compact(PackedContigs{b}, loci, contigs + contigBase, contigs_cap, seq_arena, seq_arena_cap, seq_arena_used, bits_arena,
+                               bits_arena_cap, bits_arena_used, contigBase, seqBase, bitsBase, lBegin, lEnd);
   if (rc != MANTA_OK && !perItemCode(rc)) return rc;
-  return spanningCompactAlign(b, loci, alignments, cigar_arena, cigar_arena_cap, cigarBase, cigar_arena_used, lBegin, lEnd, cellsOut, ptrBytesOut, rc);
-}
-/// the second half of spanningCompact (as smallsvCompactAlign)
-inline int spanningCompactAlign(
-    manta_spanning* b, const manta_asm_locus_result_t* loci, manta_spanning_alignment_t* alignments, uint32_t* cigar_arena, uint64_t cigar_arena_cap,
-    uint64_t cigarBase, uint64_t* cigar_arena_used, uint32_t lBegin, uint32_t lEnd, uint64_t* cellsOut, uint64_t* ptrBytesOut, int worst)
-{
-  manta_ctx_t* ctx = b->ctx;
-  lEnd             = std::min(lEnd, b->nLoci);
-  uint64_t used = 0, cells = 0, ptrBytes = 0;
-  for (uint32_t l = lBegin; l < lEnd; ++l) {
-    if (loci[l].status != MANTA_OK) continue;
-    for (uint32_t c = 0; c < loci[l].n_contigs; ++c) {
-      manta_spanning_alignment_t& a(alignments[loci[l].first_contig + c]);
-      std::memset(&a, 0, sizeof(a));
-      const PackedContigOut& h(b->hPacked[b->hFirst[l] + c]);
-      const bool             uncut = h.a != 0;
-      a.is_uncut                   = uncut ? 1 : 0;
-      if (h.info_status != 0 || h.res_status != 0 || h.bucket < 0) {
-        a.align.status = (h.info_status == 5) ? MANTA_E_DEVICE_FAULT : (h.info_status == 6) ? MANTA_E_EMPTY_SEQ : MANTA_E_UNSUPPORTED;
-        worst          = a.align.status;
-        continue;
-      }
-      const uint64_t n = uint64_t(h.cigar1_len) + h.cigar2_len;
-      if (used + n > cigar_arena_cap) return fail(ctx, MANTA_E_CAPACITY, "manta_spanning_download: cigar arena too small");
-      std::memcpy(cigar_arena + used, b->hCig + h.cigar_off, sizeof(uint32_t) * n);
-      a.align.score            = h.score;
-      a.align.is_jumped        = h.is_jumped;
-      a.align.begin_pos1       = h.begin1 + (uncut ? 0 : b->hostCuts[l].a1Lead);  // SVCandidateAssemblyRefiner.cpp:1716-1717
-      a.align.begin_pos2       = h.begin2 + (uncut ? 0 : b->hostCuts[l].a2Lead);
-      a.align.jump_insert_size = h.jump_insert_size;
-      a.align.jump_range       = h.jump_range;
-      a.align.cigar1_len       = h.cigar1_len;
-      a.align.cigar2_len       = h.cigar2_len;
-      a.align.cigar1_off       = cigarBase + used;
-      a.align.cigar2_off       = cigarBase + used + h.cigar1_len;
-      used += n;
-      cells += uint64_t(h.query_len) * h.ref_len;
-      ptrBytes += (uint64_t(h.query_len) + 1) * (uint64_t(h.ref_len) + 2);
-    }
-  }
-  if (cellsOut) {
-    *cellsOut    = cells;
-    *ptrBytesOut = ptrBytes;
-  } else {
-    b->stats.dp_cells         = cells;
-    b->stats.ptr_matrix_bytes = ptrBytes;
-  }
-  if (cigar_arena_used) *cigar_arena_used = used;
-  if (worst != MANTA_OK) return fail(ctx, worst, "manta_spanning_download: one or more loci/contigs failed; see per-item status");
-  return MANTA_OK;
+  return compactAlign(b, loci, alignments, cigar_arena, cigar_arena_cap, cigarBase, cigar_arena_used, lBegin, lEnd, cellsOut, ptrBytesOut, rc);
 }
 
-/// CIGAR words spanningCompact writes for the loci [lBegin, lEnd)
-inline uint64_t spanningCigarWords(const manta_spanning* b, uint32_t lBegin, uint32_t lEnd)
+/// CIGAR words compact() writes for the loci [lBegin, lEnd)
+template <typename Pipe>
+uint64_t cigarWords(const Pipe* b, uint32_t lBegin, uint32_t lEnd)
 {
   uint64_t n = 0;
   for (uint32_t l = lBegin; l < lEnd; ++l) {
@@ -2092,13 +2026,10 @@ inline uint64_t spanningCigarWords(const manta_spanning* b, uint32_t lBegin, uin
     if (h.status != ASM_OK) continue;
     for (uint32_t c = 0; c < h.n_contigs; ++c) {
       const PackedContigOut& pc(b->hPacked[b->hFirst[l] + c]);
-      if (pc.info_status == 0 && pc.res_status == 0 && pc.bucket >= 0) n += uint64_t(pc.cigar1_len) + pc.cigar2_len;
+      if (packedAligned(pc)) n += alignmentRecord(b, l, c, pc, 0, nullptr, nullptr);
     }
   }
   return n;
 }
 
 }  // namespace manta_host
-using namespace manta_host;
-
-using namespace manta_host;

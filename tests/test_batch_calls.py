@@ -222,3 +222,162 @@ def test_gpu_batch_odd_shapes_and_repeats(gpu):
     for rep in range(6):
         stress_shapes(gpu, [(257, 64, 2), (40, 0, 1)], 950 + rep)
     check_history_across_different_batches(gpu, 120)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# error exits and pipeline-dependent statistics of the whole-batch calls, each for both pipelines
+# ---------------------------------------------------------------------------------------------------------------
+SMALL_OPTS = asm_opts(minWordLength=25, maxWordLength=45)
+SPAN_OPTS = asm_opts(minWordLength=25, maxWordLength=45, minContigLength=40)
+FULL_CAPS = (1 << 20, 1 << 16, 1 << 18)
+KINDS = ("smallsv", "spanning")
+
+
+def family_inputs(kind, n):
+    """(the batch tuple of the call, what the oracle comparison of one locus needs)"""
+    if kind == "smallsv":
+        batch = small_batch(n, 4242)
+        batch = batch[:5] + (np.tile(np.array([40, 40, 200, 200], dtype=np.int32), (n, 1)),)
+        return batch, batch
+    loci, cuts, batch = spanning_case(n)
+    return batch, (loci, cuts)
+
+
+def family_call(lib, kind, batch, out, scores=None, **kw):
+    if kind == "smallsv":
+        return lib.smallsv_batch(SMALL_OPTS, scores or SCORES, -100, batch, out, **kw)
+    return lib.spanning_batch(SPAN_OPTS, scores or SPAN_SC, -100, batch, out, **kw)
+
+
+def assert_locus_equals_oracle(kind, oracle, src, r, l):
+    if kind == "smallsv":
+        reads, ref, cuts = unpack_locus(src, l)
+        assert small_sv_text(r) == oracle.small_sv_locus(SMALL_OPTS, SCORES, -100, reads, ref, cuts), l
+    else:
+        loci, cuts = src
+        want = oracle_locus(oracle, SPAN_OPTS, loci[l][0], loci[l][1], loci[l][2], cuts[l])[1]
+        got = [(a["score"], a["jump_insert_size"], a["jump_range"], a["begin1"], a["cigar1"], a["begin2"], a["cigar2"], a["is_uncut"])
+               for a in r["aligns"]]
+        assert got == want, l
+
+
+def arenas_too_small(lib, oracle, kind):
+    """a contig-text, read-set or CIGAR arena that cannot hold the first block: MANTA_E_CAPACITY under the call's own name, and the
+    pooled pipelines serve the next call as if nothing had happened"""
+    n = 6
+    batch, _ = family_inputs(kind, n)
+    for workers in (1, 2):
+        for caps in ((16, 1 << 16, 1 << 18), (1 << 20, 1, 1 << 18), (1 << 20, 1 << 16, 1)):
+            out = BatchOutput(lib, kind, n, 10, *caps)
+            with pytest.raises(MantaError) as err:
+                family_call(lib, kind, batch, out, block_loci=2, n_workers=workers)
+            assert err.value.code == -6 and "manta_%s_batch: caller arenas too small" % kind in str(err.value), (workers, caps)
+        if kind == "smallsv":
+            check_smallsv(lib, oracle, n, block=2, workers=workers, mixed=False)
+        else:
+            check_spanning(lib, oracle, n, block=2, workers=workers)
+
+
+def refused_block(lib, oracle, kind):
+    """one locus outside the envelope: its block's loci carry the code, the other blocks are served and counted"""
+    n = 6
+    batch, src = family_inputs(kind, n)
+    min_wl = np.full(n, 25, dtype=np.uint32)
+    max_wl = np.full(n, 45, dtype=np.uint32)
+    max_wl[2] = 200
+    out = BatchOutput(lib, kind, n, 10, *FULL_CAPS)
+    family_call(lib, kind, batch, out, min_wl=min_wl, max_wl=max_wl, block_loci=2, n_workers=2, strict=False)
+    assert [out.res[l].status for l in range(n)] == [0, 0, -5, -5, 0, 0]
+    res = out.decode(np.diff(batch[2]))
+    for l in (0, 1, 4, 5):
+        assert_locus_equals_oracle(kind, oracle, src, res[l], l)
+    st = out.stats_dict()
+    assert st["n_blocks"] == 3 and st["n_loci_lds_small"] == 4  # (the refused block is not counted)
+    with pytest.raises(MantaError) as err:
+        family_call(lib, kind, batch, BatchOutput(lib, kind, n, 10, *FULL_CAPS), min_wl=min_wl, max_wl=max_wl, block_loci=2, n_workers=2,
+                    strict=True)
+    assert err.value.code == -5 and "per-locus word length outside 1..128" in str(err.value)
+
+
+def call_level_refusals(lib, kind):
+    n = 6
+    batch, _ = family_inputs(kind, n)
+
+    def refused(b, what, scores=None, **kw):
+        with pytest.raises(MantaError) as err:
+            family_call(lib, kind, b, BatchOutput(lib, kind, n, 10, *FULL_CAPS), scores=scores, block_loci=2, n_workers=2, **kw)
+        assert err.value.code == -1 and what in str(err.value), what
+
+    refused(batch, "manta_%s_batch: per-locus word lengths need both arrays" % kind, min_wl=np.full(n, 25, dtype=np.uint32))
+    at = 4 if kind == "smallsv" else 6  # ref_off / ref2_off
+    off = batch[at].copy()
+    off[[2, 3]] = off[[3, 2]]
+    refused(batch[:at] + (off,) + batch[at + 1:], "offsets not monotone")
+    if kind == "spanning":
+        refused(batch, "isAllowEdgeInsertion", scores=SPAN_SC[:5] + [1])
+
+
+def pipeline_statistics(lib, kind):
+    n, block = 7, 3
+    batch, _ = family_inputs(kind, n)
+    out = BatchOutput(lib, kind, n, 10, *FULL_CAPS)
+    family_call(lib, kind, batch, out, block_loci=block, n_workers=2)
+    st = out.stats_dict()
+    read_off, begin = batch[1], batch[2]
+    ref_offs = (batch[4],) if kind == "smallsv" else (batch[4], batch[6])
+    blocks = (n + block - 1) // block
+    n_reads = int(begin[-1] - begin[0])
+    want = int(read_off[begin[-1]] - read_off[begin[0]]) + 8 * (n_reads + blocks) + sum(int(o[-1] - o[0]) for o in ref_offs) + \
+        (4 + 8 * len(ref_offs)) * (n + blocks) + 16 * n
+    print(kind, "h2d_bytes", st["h2d_bytes"], "expected", want, "n_alignments", st["n_alignments"])
+    assert st["h2d_bytes"] == want
+    assert st["n_blocks"] == blocks == 3
+    res = out.decode(np.diff(begin))
+    # every contig is aligned once; the spanning pipeline aligns a contig that ends up against the uncut references a second time
+    n_align = sum(len(r["aligns"]) for r in res) + (sum(a["is_uncut"] for r in res for a in r["aligns"]) if kind == "spanning" else 0)
+    assert st["n_alignments"] == n_align
+    assert st["n_loci_lds_small"] + st["n_loci_lds_big"] + st["n_loci_general"] == n
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_emulated_batch_arenas_too_small(emu, oracle, kind):
+    arenas_too_small(emu, oracle, kind)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_emulated_batch_refused_block(emu, oracle, kind):
+    refused_block(emu, oracle, kind)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_emulated_batch_call_level_refusals(emu, kind):
+    call_level_refusals(emu, kind)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_emulated_batch_pipeline_statistics(emu, kind):
+    pipeline_statistics(emu, kind)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+def test_gpu_batch_arenas_too_small(gpu, oracle, kind):
+    arenas_too_small(gpu, oracle, kind)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+def test_gpu_batch_refused_block(gpu, oracle, kind):
+    refused_block(gpu, oracle, kind)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+def test_gpu_batch_call_level_refusals(gpu, kind):
+    call_level_refusals(gpu, kind)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+def test_gpu_batch_pipeline_statistics(gpu, kind):
+    pipeline_statistics(gpu, kind)

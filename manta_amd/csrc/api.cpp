@@ -279,8 +279,9 @@ int refCopies(manta_spanning* b, const char* who, uint32_t n_loci, RefCopies& ou
 
 /// The four upload calls (`who`; the caller has checked its pointers): plan the assembler, validate the references, then the reads and
 /// behind them the references.  Streamed (whole-batch calls, `mayStream`): the reads travel in chunks on the copy stream behind the
-/// running assembler; the assembler does not read the reference windows, so they follow on the same stream and the schedule kernel waits
-/// for them (refsReady) -- nothing but the small per-read arrays is waited for here.  Otherwise everything is on the device at return.
+/// running assembler; the graph kernels do not read the reference windows, so they follow on the same stream and what does read them waits
+/// for them (refsReady: the small-SV contig kernels, whose epilogue trims against the windows, and the schedule kernels) -- nothing but
+/// the small per-read arrays is waited for here.  Otherwise everything is on the device at return.
 template <typename Pipe, typename... Refs>
 int pipeUpload(Pipe* b, const char* who, uint32_t n_loci, const ReadsIn& rd, bool mayStream, Refs... refs)
 {
@@ -641,14 +642,60 @@ int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates)
     SmallSvTaskInfo* dInfo    = b->dInfo.as<SmallSvTaskInfo>(nSlots);
     AlignResultDev*  dResults = b->dResults.as<AlignResultDev>(nSlots);
     uint32_t*        dBuckets = b->dBucketIds.as<uint32_t>(nSlots * kNumESet);
-    uint32_t*        dSmall   = b->dSmall.as<uint32_t>(64);  // [0..11] counts, [16..27] maxref, [32] sched counter, [34..35] cigar_used, [40..51] align counters
+    // [0..11] counts, [16..27] maxref, [32] sched counter, [34..35] cigar_used, [40..51] align counters, [64..] one byte per locus: scheduled by
+    // the contig kernels' epilogue (per pipeline and never downloaded: the epilogue writes it, the task records and the bucket lists under the
+    // assembler's gate, where another pipeline of the device may be aligning)
+    const uint64_t   smallWords = 64 + (uint64_t(nLoci) + 3) / 4;
+    uint32_t*        dSmall   = b->dSmall.as<uint32_t>(smallWords);
     const uint32_t   tableCap = nextPow2(2ull * as.maxContigLen);
     const int        schedWaves = std::getenv("MANTA_AMD_SCHED_WAVES_PER_CU") ? std::max(1, std::atoi(std::getenv("MANTA_AMD_SCHED_WAVES_PER_CU"))) : 12;
     const uint32_t   schedChunk = std::getenv("MANTA_AMD_SCHED_CHUNK") ? uint32_t(std::max(1, std::atoi(std::getenv("MANTA_AMD_SCHED_CHUNK")))) : 2u;
     const int        schedGrid = rt::roundGrid(int(std::min<uint64_t>((nLoci + schedChunk - 1) / schedChunk, uint64_t(std::max(1, ctx->cuCount * schedWaves)))));
     uint32_t*        dTable   = b->dTable.as<uint32_t>(uint64_t(tableCap) * schedGrid);
-    rt::dzero(dSmall, sizeof(uint32_t) * 64);
+    rt::dzero(dSmall, sizeof(uint32_t) * smallWords);
     rt::dzero(dResults, sizeof(AlignResultDev) * nSlots);
+    // The 10-mer trim and the task set-up of a locus run in the epilogue of the LDS contig kernels wherever the locus' LDS share holds the
+    // trim's table and texts (asm_contig.hpp: scheduleEpilogue); smallsv_schedule_kernel below takes the loci that are left.
+    // MANTA_AMD_NO_FUSED_SCHEDULE (A/B knob, read per call: the tests flip it): everything through smallsv_schedule_kernel.
+    const bool fusedSchedule = std::getenv("MANTA_AMD_NO_FUSED_SCHEDULE") == nullptr;
+    ScheduleParams S{};
+    S.loci               = as.dLoci;
+    S.contigs            = as.dCont;
+    S.seq_arena          = as.dSeq;
+    S.n_loci             = nLoci;
+    S.max_assembly_count = maxAsm;
+    S.refs               = static_cast<const uint8_t*>(b->dRefs.p);
+    S.ref_off            = static_cast<const uint64_t*>(b->dRefOff.p);
+    S.cuts               = static_cast<const SmallSvCuts*>(b->dCuts.p);
+    S.tasks              = dTasks;
+    S.info               = dInfo;
+    S.bucket_ids         = dBuckets;
+    S.bucket_count       = dSmall;
+    S.bucket_maxref      = dSmall + 16;
+    S.cigar_used         = reinterpret_cast<unsigned long long*>(dSmall + 34);
+    // (the epilogue runs before the text arena's use is known.  A task's region, 8 words per text byte from 8 x its text offset, ends
+    // below 8 x the end of its text + 64, and a text that was emitted lies inside the arena: the bound never refuses a contig, here or below)
+    S.cigar_cap          = 8ull * as.devSeqCap + 64;
+    S.counter            = dSmall + 32;
+    S.table_ws           = dTable;
+    S.table_cap          = tableCap;
+    S.chunk              = schedChunk;
+    schedPackE(S, kESet, unsigned(kNumESet));
+    S.marks              = fusedSchedule ? reinterpret_cast<uint8_t*>(dSmall + 64) : nullptr;
+    S.n_marked           = reinterpret_cast<unsigned long long*>(as.dCnt + AsmStage::kCntScheduled);  // (comes back with asmCnt)
+    const ScheduleParams* dSched = nullptr;
+    if (fusedSchedule) {
+      // (the block holds this pipeline's buffers and sizes: from the second run of equal blocks on it is what the device already
+      // has, and nothing is copied.  Measured: a copy per run from page-locked memory cost the step 0.03 ms on the device's side)
+      ScheduleParams* d = b->dSchedArgs.as<ScheduleParams>(1);
+      if (!b->schedArgsValid || std::memcmp(&b->schedArgsLast, &S, sizeof(S)) != 0) {
+        b->schedArgsValid = false;
+        rt::h2d(d, &S, sizeof(S));  // (pageable source: staged before the call returns)
+        std::memcpy(&b->schedArgsLast, &S, sizeof(S));
+        b->schedArgsValid = true;
+      }
+      dSched = d;
+    }
 
     const bool dbg = std::getenv("MANTA_AMD_DEBUG") != nullptr;
     auto       stage = [&](const char* what) {
@@ -658,7 +705,7 @@ int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates)
       std::fflush(stderr);
     };
     stage("start");
-    uint64_t asmCnt[4];  // [1] text bytes, [3] capacity failures
+    uint64_t asmCnt[AsmStage::kCntScheduled + 1];  // [1] text bytes, [3] capacity failures, [16] loci scheduled by the contig kernels' epilogue
     {
       GateLock only(gates, &StageGates::asmMu);
       // A streamed-upload assembler polls for chunks whose copies may need a free workgroup slot (launch() leaves some);
@@ -669,6 +716,19 @@ int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates)
       as.stageQueued = false;  // (a run that failed behind its queued staging must not leave the flag to the next one)
       as.earlyStaged = false;
       b->evStart.record();
+      // (the epilogue reads the reference windows: the contig kernels -- not the graph kernels -- wait for a streamed upload's)
+      struct SchedScope {
+        AsmStage& as;
+        ~SchedScope()
+        {
+          as.sched      = nullptr;
+          as.schedWaits = nullptr;
+        }
+      } schedScope{as};
+      if (fusedSchedule) {
+        as.sched      = dSched;
+        as.schedWaits = b->refsOnCopy ? &b->refsReady : nullptr;
+      }
       as.launch();
       b->evAsm.record();
       // loci that did not fit the typical-case workspace run again here (rare; the counter rides on a wait that is there anyway
@@ -695,29 +755,23 @@ int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates)
     GateLock alignOnly(gates, &StageGates::alignMu);
     if (b->refsOnCopy) rt::curStreamWaits(b->refsReady);  // reference windows of a streamed upload (manta_smallsv_upload)
 
-    ScheduleParams S;
-    S.loci               = as.dLoci;
-    S.contigs            = as.dCont;
-    S.seq_arena          = as.dSeq;
-    S.n_loci             = nLoci;
-    S.max_assembly_count = maxAsm;
-    S.refs               = static_cast<const uint8_t*>(b->dRefs.p);
-    S.ref_off            = static_cast<const uint64_t*>(b->dRefOff.p);
-    S.cuts               = static_cast<const SmallSvCuts*>(b->dCuts.p);
-    S.tasks              = dTasks;
-    S.info               = dInfo;
-    S.bucket_ids         = dBuckets;
-    S.bucket_count       = dSmall;
-    S.bucket_maxref      = dSmall + 16;
-    S.cigar_used         = reinterpret_cast<unsigned long long*>(dSmall + 34);
-    S.cigar_cap          = cigarCap;
-    S.counter            = dSmall + 32;
-    S.table_ws           = dTable;
-    S.table_cap          = tableCap;
-    S.n_e                = kNumESet;
-    S.chunk              = schedChunk;
-    for (int i = 0; i < kNumESet; ++i) S.e_set[i] = uint32_t(kESet[i]);
-    rt::launch(smallsv_schedule_kernel, schedGrid, SCHED_LDS_BYTES, S);
+    // what the epilogue left: loci handed to assemble_kernel, capacity re-runs, loci outside the small LDS class or with a share too
+    // small for the trim, everything on the general path.  Its grid follows their number (with asmCnt: no wait of its own); none: no launch.
+    const uint64_t nFused   = fusedSchedule ? std::min<uint64_t>(asmCnt[AsmStage::kCntScheduled], nLoci) : 0;
+    const uint64_t nUnfused = nLoci - nFused;
+    if (dbg) std::fprintf(stderr, "manta_amd: smallsv schedule: %llu loci in the contig kernels' epilogue, %llu left to smallsv_schedule_kernel\n",
+                          (unsigned long long)nFused, (unsigned long long)nUnfused);
+    if (nUnfused) {
+      S.cigar_cap = cigarCap;
+      int grid    = schedGrid;
+      if (fusedSchedule) {
+        // few loci among many marked ones: a pop covers 64 loci (one mark each per lane), so that no wave walks a long run of marks
+        if (nUnfused * 8 <= nLoci) S.chunk = 64;
+        S.chunk = std::min<uint32_t>(S.chunk, 64);
+        grid    = rt::roundGrid(int(std::min<uint64_t>((S.chunk == 64) ? (nLoci + 63) / 64 : (nUnfused + S.chunk - 1) / S.chunk + (nLoci + 2047) / 2048, uint64_t(schedGrid))));
+      }
+      rt::launch(smallsv_schedule_kernel, grid, SCHED_LDS_BYTES, S);
+    }
     // the pair-eligible buckets by descending reference length (bucket_sort_kernel): their align kernels read the sorted lists
     uint32_t  pairMask       = 0;
     uint32_t* dBucketsSorted = nullptr;

@@ -474,6 +474,9 @@ struct AsmStage {
   uint8_t*            dSeq   = nullptr;
   uint64_t*           dBits  = nullptr;
   uint64_t*           dCnt   = nullptr;
+  static constexpr int kCntQwords = 24, kCntScheduled = 16;  // dCnt[16]: loci scheduled by the contig kernels' small-SV epilogue
+  const manta_dev::ScheduleParams* sched = nullptr;  // the small-SV pipeline's scheduling block (device memory) for launch(); nullptr: none
+  rt::Event*                       schedWaits = nullptr;  // ... and what its contig kernels wait for (the reference windows of a streamed upload)
   uint8_t*            dWs    = nullptr;
   uint32_t*           dGrowth = nullptr;
 
@@ -900,7 +903,7 @@ struct AsmStage {
     dCont   = bContigs.as<AsmContigOut>(uint64_t(nLoci) * opt.max_assembly_count);
     dSeq    = bSeqArena.as<uint8_t>(devSeqCap);
     dBits   = bBitsArena.as<uint64_t>(devBitsCap);
-    dCnt    = bCounters.as<uint64_t>(16);
+    dCnt    = bCounters.as<uint64_t>(kCntQwords);
     dWs     = bWs.as<uint8_t>(stride * grid);
     dGrowth = bGrowth.as<uint32_t>(2 * ctx->growthSize.size() + 2);
     dOrder  = bOrder.as<uint32_t>(nLoci);
@@ -952,7 +955,7 @@ struct AsmStage {
 
   void launch()
   {
-    rt::dzero(dCnt, sizeof(uint64_t) * 16);
+    rt::dzero(dCnt, sizeof(uint64_t) * kCntQwords);
     rt::dfill(dLoci, 0xff, sizeof(AsmLocusOut) * nLoci);
     AsmParams P;
     P.bases            = dBases;
@@ -1057,6 +1060,8 @@ struct AsmStage {
       A.G.rws_stride = 0;
       A.G.gws        = nullptr;
       A.G.rprof      = nullptr;
+      // the small-SV pipeline's scheduling rides in the small class' contig kernels (smallsvRunImpl sets `sched` for its launch)
+      A.G.sched      = sched;
       // streamed upload: a chunk the runtime moves with a shader copy -- and every hipStreamWriteValue32, a one-workgroup kernel --
       // needs a free workgroup slot: graph_kernel's two workgroups per CU own all 160 KB of LDS and every VGPR, so a few slots stay
       // free (streamFreeSlots) -- without them the copies never run and the persistent workgroups wait for their chunks forever
@@ -1084,6 +1089,8 @@ struct AsmStage {
       auto launchSmallContigs   = [&] {
         if (smallContigsLaunched) return;
         smallContigsLaunched = true;
+        // (their epilogue reads the reference windows, which a streamed upload sends behind the reads: the graph kernels above do not wait)
+        if (sched && schedWaits) rt::curStreamWaits(*schedWaits);
         for (unsigned c = 0; c < LG_CLASSES && !fastIds.empty(); ++c) {
           if (!classBytes[c]) continue;
           A.G.cls       = c;
@@ -1100,6 +1107,7 @@ struct AsmStage {
         // the big class: its own work list (behind the small class' in dOrder), class lists and counters; slabs and punts shared
         LgArgs B         = A;
         B.G.cost_bins    = nullptr;
+        B.G.sched        = nullptr;  // (the big class is left to smallsv_schedule_kernel)
         B.P.n_loci       = uint32_t(bigIds.size());
         B.P.locus_ids    = dOrder + fastIds.size();
         B.P.counter      = reinterpret_cast<uint32_t*>(dLg + 7);
@@ -1642,8 +1650,10 @@ struct manta_smallsv : PipeBase {
   static constexpr bool        kEarlyStream   = true;  // a streamed upload of read bases starts its DMA before plan() (AsmStage::startStream)
   int32_t               largeIndel = 0;
   uint64_t              refBytes = 0, maxRef = 0;
-  DevBuf                dRefs, dRefOff, dTable;
+  DevBuf                dRefs, dRefOff, dTable, dSchedArgs;  // (dSchedArgs: the ScheduleParams of the contig kernels' epilogue)
   PinnedBuf             pSmall;
+  manta_dev::ScheduleParams schedArgsLast{};  // what dSchedArgs holds (schedArgsValid), so that an unchanged block is not uploaded again
+  bool                  schedArgsValid = false;
   uint32_t              lastSmall[40] = {0};  // bucket counters of the previous run (grids of the next one)
   bool                  bucketHistory = false;
   // contig QC behind the aligners (manta_smallsv_set_qc; off unless asked for)

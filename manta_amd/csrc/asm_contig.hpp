@@ -83,6 +83,8 @@ struct LdsContig {
   uint16_t*        corePrefix;
   unsigned         candSlotV;  // lane c: cache slot that holds candidate c's walk
   uint64_t         tMark;
+  // small-SV scheduling epilogue (scheduleEpilogue): bytes of LDS at `lds` that are this locus' own (set by the kernel body; 0: no epilogue)
+  unsigned         shareBytes;
 
   WV_DEV LdsContig(const AsmParams& p, const LgParams& g, char* base, uint8_t* ws) : P(p), G(g), lds(base)
   {
@@ -106,6 +108,7 @@ struct LdsContig {
     seqWords  = CK_SEQ_WORDS;
     candSlotV = 0;
     nCand     = 0;
+    shareBytes = 0;
     cyclic = anyRep = false;
     nPseudo = nCore = visDw = 0;
     coreBits = repBits = vis = nullptr;
@@ -1302,6 +1305,75 @@ struct LdsContig {
       }
     }
     if (lane == 0) P.loci[locus] = out;
+    if (!C::BIG && G.sched && shareBytes) scheduleEpilogue(locus, seqBase, finalCount, myLen, chosen, chosenHi);
+  }
+
+  /// The small-SV pipeline's work for the contigs of this locus, done by the wave that has just emitted them: exactly what
+  /// smallsv_schedule_kernel does per locus (smallsv_trim.hpp: scheduleContig -- trim, task and info records; here one bucket-list
+  /// append per contig), without that kernel's launch, its tail and its chains of dependent reads of records this wave still holds.
+  /// The graph in LDS is done with, so the 10-mer table and the staged texts take its place.  The contig texts are read back from
+  /// seq_arena: this wave's own stores, drained by the wv::sync() below before any lane loads them.  `myLen` / `chosen` / `chosenHi`:
+  /// selectAndEmit's candidate lengths (lane c) and choices.
+  ///   A locus with a contig whose table does not fit SCHED_TABLE_BYTES, or whose texts do not fit the rest of the share, is left
+  /// alone and unmarked -- nothing of it is written here --, and smallsv_schedule_kernel takes it.  So does every locus that never
+  /// gets here (punted, out of arena capacity, the big class, the general path).
+  WV_DEV void scheduleEpilogue(const unsigned locus, const uint64_t seqBase, const unsigned finalCount, const unsigned myLen, const uint64_t chosen,
+                               const uint64_t chosenHi)
+  {
+    // (a block in device memory, not in the kernel's argument: its two dozen fields are loaded here, once per locus -- as arguments
+    // they stayed in scalar registers across the whole contig loop and cost it a hundred spills)
+    const ScheduleParams& S = *G.sched;
+    auto lenAt = [&](const unsigned f) { return wv::readlane(myLen, int(((f < 10) ? (chosen >> (6 * f)) : (chosenHi >> (6 * (f - 10)))) & 63u)); };
+    if (shareBytes <= SCHED_TABLE_BYTES + 16) return;
+    const unsigned lseqBytes = (shareBytes - SCHED_TABLE_BYTES) & ~15u;
+    const uint64_t ro0 = wv::readlane(uint64_t(S.ref_off[locus]), 0), ro1 = wv::readlane(uint64_t(S.ref_off[locus + 1]), 0);
+    if (ro1 < ro0 || ro1 - ro0 > lseqBytes) return;
+    const unsigned refSize = unsigned(ro1 - ro0);
+    bool           fits    = true;
+    for (unsigned f = 0; f < finalCount; ++f) {
+      const unsigned len = lenAt(f);
+      if (!schedTableFitsLds(len) || schedStagedBytes(len, refSize) > lseqBytes) fits = false;
+    }
+    if (!fits) return;
+    wv::sync();  // every lane is done with the graph in LDS, and this wave's text stores are visible to all its lanes
+    uint32_t* const ltable = reinterpret_cast<uint32_t*>(lds);
+    uint8_t* const  lseq   = reinterpret_cast<uint8_t*>(lds) + SCHED_TABLE_BYTES;
+    const unsigned  maxAsm = S.max_assembly_count, total = S.n_loci * maxAsm;
+    // the slots without a contig: one lane each
+    if (lane >= finalCount && lane < maxAsm) {
+      SmallSvTaskInfo none = {0, 0, 0, -1};
+      S.info[locus * maxAsm + lane] = none;
+    }
+    uint64_t so  = seqBase;
+    unsigned cig = 0;
+    for (unsigned f = 0; f < finalCount; ++f) {
+      const unsigned        len  = lenAt(f);
+      const unsigned        slot = locus * maxAsm + f;
+      const SmallSvTaskInfo info = scheduleContig(S, slot, locus, so, len, ltable, lseq, lseqBytes, nullptr);
+      wv::sync();  // single reconvergence point of every exit of scheduleContig
+      const int bucket = wv::first(info.bucket);
+      if (lane == 0) {
+        S.info[slot] = info;
+        if (bucket >= 0) {
+          // (one atomic per contig and list: ~1.6 per locus, spread over the kernel's whole run)
+          const unsigned b       = unsigned(bucket);
+          const unsigned winLen  = refSize - unsigned(info.adj_leading_cut) - unsigned(info.adj_trailing_cut);
+          const unsigned slabLen = schedSlabLen(S, b, len, winLen);
+          S.bucket_ids[size_t(b) * total + wv::atomic_add(&S.bucket_count[b], 1u)] = slot;
+          if (wv::atomic_load(&S.bucket_maxref[b]) < slabLen) wv::atomic_max(&S.bucket_maxref[b], slabLen);
+        }
+      }
+      if (bucket >= 0) cig += 4 * len + 16;
+      so += len;
+      wv::sync();  // (the next contig's table and texts overwrite this one's)
+    }
+    // the locus is done: its mark, the count the host sizes smallsv_schedule_kernel's grid from, and the CIGAR words of its tasks
+    // (manta_smallsv_output_sizes) -- two atomics nobody waits for
+    if (lane == 0) {
+      S.marks[locus] = 1;
+      wv::atomic_add(S.n_marked, 1ull);
+      if (cig) wv::atomic_add(S.cigar_used, (unsigned long long)cig);
+    }
   }
 
   /// CK_DONE: results emitted.  CK_PUNT: nothing emitted, the general path takes the locus.
@@ -1394,6 +1466,7 @@ WV_DEV void contigKernelBody(const LgArgs& A)
     if (slot >= nLoci) break;
     const unsigned locus = ids[slot];
     LdsContig<C>   c(P, G, lds, ws);
+    c.shareBytes = P.lds_bytes;  // (single-wave workgroups: the launch's whole LDS)
     const int      rc = c.run(locus);
     wv::sync();
     if (rc == CK_PUNT && wv::lane() == 0) P.punt_ids[wv::atomic_add(P.punt_count, 1u)] = locus;
@@ -1513,6 +1586,7 @@ WV_DEV void contigPoolBody(const LgArgs& A)
     const unsigned units = (needU < capU) ? needU : capU;
     char*          lds   = pool + ckPoolTake(pool, w, units, G.cost_bins ? G.cost_bins + CK_BIN_STAT : nullptr);
     LdsContig<C>   c(P, G, lds, ws);
+    c.shareBytes = 16 * units;
     const int      rc = c.run(locus);
     wv::sync();
     if (wv::lane() == 0) wv::atomic_store(reinterpret_cast<uint32_t*>(pool) + 1 + w, 0u);  // the share goes back

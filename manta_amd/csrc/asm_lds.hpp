@@ -28,6 +28,7 @@
 // memory.  Nothing is approximated.
 #pragma once
 #include "assemble_kernels.hpp"
+#include "smallsv_trim.hpp"  // ScheduleParams, scheduleContig: the contig kernels' small-SV epilogue (asm_contig.hpp)
 
 namespace manta_dev {
 
@@ -400,6 +401,8 @@ struct LgParams {
   uint64_t            rws_stride;
   uint8_t*            gws;         ///< graph_big_kernel workspaces (one per workgroup: LGL_GWS_BYTES -- the overflow read sets, the lexicographic ranks)
   unsigned long long* rprof;       ///< [8] repeat_big_kernel: shader clocks by phase, summed over its loci (debug line; nullptr: not kept)
+  // ---- the small-SV pipeline's scheduling in the small class' contig kernels (asm_contig.hpp: scheduleEpilogue); nullptr: none
+  const ScheduleParams* sched;     ///< device memory
 };
 
 static const uint32_t LG_FLAG_NO_PROOF = 1u;  ///< tests / A-B runs: never skip contig_kernel's cycle test

@@ -6,257 +6,21 @@
 #pragma once
 #include "align_kernels.hpp"
 #include "assemble_kernels.hpp"
+#include "smallsv_trim.hpp"  // the trim itself (scheduleContig): shared with the contig kernels' epilogue (asm_contig.hpp)
 
 namespace manta_dev {
 
-static const int      SMALLSV_MER       = 10;    // SVCandidateAssemblyRefiner.cpp:1986
-static const unsigned SCHED_TABLE_BYTES = 4096;  // per wavefront: 10-mer table of contigs up to 512 bp lives in LDS
-static const unsigned SCHED_SEQ_BYTES   = 6144;  // ... and so do the contig and the reference window (staged with wide loads: the scans
-                                                 // below read a byte per lane and 55 positions per round trip otherwise)
-static const unsigned SCHED_LDS_BYTES   = SCHED_TABLE_BYTES + SCHED_SEQ_BYTES + 1024;  // (+ the pending bucket entries) 11 KB per wavefront: 12-14 waves per CU
-
-struct SmallSvCuts {
-  int32_t leadingCut, trailingCut, maxLeadingCut, maxTrailingCut;  // :1912-1915
-};
-
-struct SmallSvTaskInfo {
-  int32_t status;  // 0 ok; else MANTA-level failure of the trim (contig shorter than a 10-mer, empty window)
-  int32_t adj_leading_cut, adj_trailing_cut;
-  int32_t bucket;  // index into the E set, -1 if not scheduled
-};
-
-struct ScheduleParams {
-  // assembler outputs (device)
-  const AsmLocusOut*  loci;
-  const AsmContigOut* contigs;
-  const uint8_t*      seq_arena;
-  uint32_t            n_loci;
-  uint32_t            max_assembly_count;
-  // references
-  const uint8_t*     refs;
-  const uint64_t*    ref_off;  // n_loci + 1
-  const SmallSvCuts* cuts;     // n_loci
-  // outputs
-  AlignTaskDev*    tasks;  // n_loci * max_assembly_count
-  SmallSvTaskInfo* info;   // same
-  uint32_t*        bucket_ids;     // n_buckets * (n_loci * max_assembly_count)
-  uint32_t*        bucket_count;   // n_buckets
-  uint32_t*        bucket_maxref;  // n_buckets
-  unsigned long long* cigar_used;  // bump allocator (u32 units)
-  uint64_t         cigar_cap;
-  uint32_t*        counter;
-  // per-workgroup 10-mer table
-  uint32_t* table_ws;
-  uint32_t  table_cap;  // power of two, >= 2 * longest contig
-  // E set
-  uint32_t e_set[16];
-  uint32_t n_e;
-  uint32_t chunk;  // loci per work-queue pop (smallsv_schedule_kernel)
-};
-
-WV_DEV unsigned merCode(const uint8_t* p, bool& valid)
+/// One contig slot of smallsv_schedule_kernel: the slot's records, then scheduleContig (smallsv_trim.hpp) on this wave's LDS.
+WV_DEV SmallSvTaskInfo scheduleSlot(const ScheduleParams& P, const unsigned slot, uint32_t* ltable, uint32_t* gtable)
 {
-  unsigned code = 0;
-  valid         = true;
-  for (int i = 0; i < SMALLSV_MER; ++i) {
-    const unsigned c = baseCode(p[i]);
-    if (c > 3) valid = false;
-    code = (code << 2) | (c & 3u);
-  }
-  return code;
-}
-
-/// 10-mer codes of 55 consecutive positions with ONE byte load per lane: lane l loads base p0+l, then the codes of
-/// bases l..l+9 are assembled by doubling with four lane shuffles (2, 4, 8, 10 bases).  Lane l (<= 54) returns the
-/// code of the 10-mer starting at p0+l; `valid` is false if the 10-mer leaves [0,len) or holds a non-ACGT base.
-/// All 64 lanes must call.
-static const int MER_BATCH = 55;
-/// the lane's base code (0..3, 4 = not ACGT / outside the sequence) for batch start p0: the only memory access of a batch
-WV_DEV unsigned merLoadBase(const uint8_t* seq, const int len, const int p0)
-{
-  const int pos = p0 + wv::lane();
-  return (pos >= 0 && pos < len) ? baseCode(seq[pos]) : 4u;
-}
-/// 10-mer codes of the batch from the per-lane base codes
-WV_DEV unsigned merCodesFromBase(const unsigned c, bool& valid)
-{
-  const int      l   = wv::lane();
-  unsigned bad = (c > 3) ? 1u : 0u;
-  unsigned w1  = c & 3u;
-  const unsigned w2 = (w1 << 2) | wv::shfl(w1, (l + 1) & 63);
-  const unsigned b2 = bad | wv::shfl(bad, (l + 1) & 63);
-  const unsigned w4 = (w2 << 4) | wv::shfl(w2, (l + 2) & 63);
-  const unsigned b4 = b2 | wv::shfl(b2, (l + 2) & 63);
-  const unsigned w8 = (w4 << 8) | wv::shfl(w4, (l + 4) & 63);
-  const unsigned b8 = b4 | wv::shfl(b4, (l + 4) & 63);
-  const unsigned w10 = (w8 << 4) | wv::shfl(w2, (l + 8) & 63);
-  const unsigned b10 = b8 | wv::shfl(b2, (l + 8) & 63);
-  valid = (l < MER_BATCH) && (b10 == 0);
-  return w10;
-}
-WV_DEV unsigned merCodes55(const uint8_t* seq, const int len, const int p0, bool& valid)
-{
-  return merCodesFromBase(merLoadBase(seq, len, p0), valid);
-}
-
-WV_DEV bool merLookup(const uint32_t* table, const unsigned mask, const unsigned code)
-{
-  unsigned s = (code * 2654435761u) & mask;
-  while (true) {
-    const uint32_t v = table[s];
-    if (v == 0) return false;
-    if (v == code + 1) return true;
-    s = (s + 1) & mask;
-  }
-}
-
-/// One contig slot: 10-mer reference trim + alignment task set-up.  Returns the slot's SmallSvTaskInfo; every exit is
-/// wave-uniform and the caller stores the record after a single reconvergence point.  (An earlier form that stored
-/// from lane 0 and `continue`d straight to the work-queue pop was compiled into a loop whose lanes left at different
-/// times -- 63 lanes then re-ran the pop's readfirstlane without lane 0 and spun forever on loci without contigs.)
-WV_DEV SmallSvTaskInfo scheduleSlot(const ScheduleParams& P, const unsigned slot, const unsigned total, uint32_t* ltable, uint32_t* gtable)
-{
-  const unsigned    lane  = unsigned(wv::lane());
   const unsigned    locus = slot / P.max_assembly_count, ci = slot % P.max_assembly_count;
   const AsmLocusOut lo    = P.loci[locus];
-  SmallSvTaskInfo   info  = {0, 0, 0, -1};
   if (lo.status != ASM_OK || ci >= lo.n_contigs) {
-    info.status = (lo.status != ASM_OK) ? 1 : 0;
-    return info;
+    SmallSvTaskInfo none = {(lo.status != ASM_OK) ? 1 : 0, 0, 0, -1};
+    return none;
   }
-  const AsmContigOut co      = P.contigs[slot];
-  const uint8_t*     contigG = P.seq_arena + co.seq_off;
-  const unsigned     clen    = co.seq_len;
-  const uint8_t*     refG    = P.refs + P.ref_off[locus];
-  const int          refSize = int(P.ref_off[locus + 1] - P.ref_off[locus]);
-  const SmallSvCuts  cuts    = P.cuts[locus];
-  // contig and reference window into LDS (16 bytes per lane and load, all in flight together) when they fit; the scans then
-  // run at LDS latency.  The task keeps the global pointers.
-  const uint8_t* contig = contigG;
-  const uint8_t* ref    = refG;
-  {
-    uint8_t* const  lseq = reinterpret_cast<uint8_t*>(ltable) + SCHED_TABLE_BYTES;
-    const uintptr_t gc = reinterpret_cast<uintptr_t>(contigG), gr = reinterpret_cast<uintptr_t>(refG);
-    const unsigned  leadC = unsigned(gc & 15), leadR = unsigned(gr & 15);
-    const unsigned  bytesC = (leadC + clen + 15) & ~15u, bytesR = (leadR + unsigned(refSize > 0 ? refSize : 0) + 15) & ~15u;
-    if (bytesC + bytesR <= SCHED_SEQ_BYTES) {
-      const u32x4* sc = reinterpret_cast<const u32x4*>(gc - leadC);
-      const u32x4* sr = reinterpret_cast<const u32x4*>(gr - leadR);
-      u32x4*       dc = reinterpret_cast<u32x4*>(lseq);
-      u32x4*       dr = reinterpret_cast<u32x4*>(lseq + bytesC);
-      for (unsigned i = lane; i < bytesC / 16; i += 64) dc[i] = sc[i];
-      for (unsigned i = lane; i < bytesR / 16; i += 64) dr[i] = sr[i];
-      wv::sync();
-      contig = lseq + leadC;
-      ref    = lseq + bytesC + leadR;
-    }
-  }
-
-  if (clen < unsigned(SMALLSV_MER) || 2 * clen > P.table_cap) {
-    info.status = 2;
-    return info;
-  }
-  // hash set of the contig's 10-mers (:1987-1991)
-  unsigned tcap = 64;
-  while (tcap < 2 * clen) tcap <<= 1;
-  const unsigned mask  = tcap - 1;
-  uint32_t*      table = (tcap * 4 <= SCHED_TABLE_BYTES) ? ltable : gtable;
-  for (unsigned i = lane; i < tcap; i += 64) table[i] = 0;
-  wv::sync();
-  for (int p0 = 0; p0 + SMALLSV_MER <= int(clen); p0 += MER_BATCH) {
-    bool           valid;
-    const unsigned code = merCodes55(contig, int(clen), p0, valid);
-    if (!valid) continue;
-    unsigned s = (code * 2654435761u) & mask;
-    while (true) {
-      const uint32_t old = wv::atomic_cas(&table[s], 0u, code + 1);
-      if (old == 0 || old == code + 1) break;
-      s = (s + 1) & mask;
-    }
-  }
-  wv::sync();
-  if (table == gtable) wv::fence_acquire();
-
-  const int minRefIndex    = cuts.leadingCut;
-  const int maxRefIndex    = refSize - (cuts.trailingCut + SMALLSV_MER);
-  const int maxFwdRefIndex = (cuts.maxLeadingCut < maxRefIndex) ? cuts.maxLeadingCut : maxRefIndex;
-  // first hit scanning forward (:1997-2001) and last hit scanning backward (:2004-2008, windows of 55 start positions, highest
-  // window first), one window of each per round: the two scans are independent, so their lane shuffles and table probes overlap
-  int adjLead = maxFwdRefIndex + 1;
-  if (adjLead < minRefIndex) adjLead = minRefIndex;  // empty scan range: the loop variable keeps its initial value
-  const int minRevRefIndex = (minRefIndex > refSize - cuts.maxTrailingCut) ? minRefIndex : (refSize - cuts.maxTrailingCut);
-  int       revIndex       = minRevRefIndex - 1;
-  if (revIndex > maxRefIndex) revIndex = maxRefIndex;  // empty scan range
-  {
-    int  fBase = minRefIndex, bTop = maxRefIndex;
-    bool fDone = fBase > maxFwdRefIndex, bDone = bTop < minRevRefIndex;
-    while (!fDone || !bDone) {
-      const int      bBase = bTop - (MER_BATCH - 1);
-      const unsigned cf = merLoadBase(ref, refSize, fDone ? -1000 : fBase), cb = merLoadBase(ref, refSize, bDone ? -1000 : bBase);
-      bool           vf, vb;
-      const unsigned codeF = merCodesFromBase(cf, vf), codeB = merCodesFromBase(cb, vb);
-      const int      iF = fBase + int(lane), iB = bBase + int(lane);
-      const bool     hitF = !fDone && vf && iF <= maxFwdRefIndex && merLookup(table, mask, codeF);
-      const bool     hitB = !bDone && vb && iB >= minRevRefIndex && iB <= bTop && merLookup(table, mask, codeB);
-      const uint64_t mF = wv::ballot(hitF), mB = wv::ballot(hitB);
-      if (!fDone) {
-        if (mF) {
-          adjLead = fBase + wv::ctz(mF);
-          fDone   = true;
-        } else {
-          fBase += MER_BATCH;
-          fDone = fBase > maxFwdRefIndex;
-        }
-      }
-      if (!bDone) {
-        if (mB) {
-          revIndex = bBase + (63 - wv::clz(mB));
-          bDone    = true;
-        } else {
-          bTop -= MER_BATCH;
-          bDone = bTop < minRevRefIndex;
-        }
-      }
-    }
-  }
-  const int adjTrail = refSize - (revIndex + SMALLSV_MER);
-  const int winLen   = refSize - adjLead - adjTrail;
-  info.adj_leading_cut  = adjLead;
-  info.adj_trailing_cut = adjTrail;
-  if (winLen <= 0 || adjLead < 0 || adjTrail < 0) {
-    info.status = 3;
-    return info;
-  }
-  int            bucket = -1;
-  const unsigned need   = (clen + 63) / 64;
-  for (unsigned b = 0; b < P.n_e; ++b)
-    if (P.e_set[b] >= need) {
-      bucket = int(b);
-      break;
-    }
-  if (bucket < 0) bucket = int(P.n_e) - 1;  // longer than 64 x 32 columns: the widest kernel runs it in strips (align_kernels.hpp)
-  // The task's CIGAR region needs no allocator: contig texts do not overlap in the text arena, so neither do regions of 8 words
-  // per contig base starting at 8 x the text offset (a task takes 4 * length + 16 words, contigs here hold >= 10 bases).  (One
-  // bump-allocator atomic per contig on ONE address, next to one per locus for the work queue and one per contig for the bucket
-  // lists, was what this kernel's 0.9 ms consisted of: ~40 k same-address L2 atomics.)
-  const unsigned long long cig = 8ull * co.seq_off;
-  if (cig + 4ull * clen + 16 > P.cigar_cap) {
-    info.status = 5;
-    return info;
-  }
-  if (lane == 0) {
-    AlignTaskDev t;
-    t.query     = contigG;
-    t.ref1      = refG + adjLead;
-    t.ref2      = nullptr;
-    t.query_len = clen;
-    t.ref1_len  = unsigned(winLen);
-    t.ref2_len  = 0;
-    t.cigar_off = uint32_t(cig);
-    P.tasks[slot] = t;
-  }
-  info.bucket = bucket;
-  return info;
+  const AsmContigOut co = P.contigs[slot];
+  return scheduleContig(P, slot, locus, co.seq_off, co.seq_len, ltable, reinterpret_cast<uint8_t*>(ltable) + SCHED_TABLE_BYTES, SCHED_SEQ_BYTES, gtable);
 }
 
 /// per-wave pending bucket entries (LDS): a bucket's list takes them eight at a time, with one atomic
@@ -316,33 +80,40 @@ WV_KERNEL void smallsv_schedule_kernel(const ScheduleParams P)
     base = wv::first(base);
     if (base >= P.n_loci) break;
     const unsigned end = (base + P.chunk < P.n_loci) ? base + P.chunk : P.n_loci;
-    for (unsigned locus = base; locus < end; ++locus) {
-      const AsmLocusOut lo       = P.loci[locus];
-      const unsigned    nContigs = (lo.status == ASM_OK) ? lo.n_contigs : 0u;
-      // slots without a contig: one lane each
-      if (lane >= nContigs && lane < P.max_assembly_count) {
-        SmallSvTaskInfo none = {(lo.status != ASM_OK) ? 1 : 0, 0, 0, -1};
-        P.info[locus * P.max_assembly_count + lane] = none;
-      }
-      for (unsigned ci = 0; ci < nContigs; ++ci) {
-        const unsigned        slot = locus * P.max_assembly_count + ci;
-        const SmallSvTaskInfo info = scheduleSlot(P, slot, total, ltable, gtable);
-        wv::sync();  // single reconvergence point of every exit of scheduleSlot
-        if (lane == 0) P.info[slot] = info;
-        if (info.bucket >= 0) {
-          const unsigned b = unsigned(info.bucket);
-          if (lane == 0) {
-            const AlignTaskDev& t = P.tasks[slot];
-            const unsigned slabLen = unsigned(alignSlabRefLen(1, int(P.e_set[b]), t.query_len, t.ref1_len));
-            pend->slot[b][pend->count[b]] = slot;
-            pend->count[b] += 1;
-            pend->cigarWords += 4 * t.query_len + 16;
-            if (slabLen > pend->maxref[b]) pend->maxref[b] = slabLen;
+    // (with marks -- the contig kernels' epilogue has scheduled those loci already -- a pop is at most 64 loci and costs one byte load per
+    // lane; without them `todo` is simply every locus of the pop, in order)
+    for (unsigned b0 = base; b0 < end; b0 += 64) {
+      uint64_t todo = wv::ballot(b0 + lane < end && !(P.marks && P.marks[b0 + lane]));
+      while (todo) {
+        const unsigned locus = b0 + unsigned(wv::ctz(todo));
+        todo &= todo - 1;
+        const AsmLocusOut lo       = P.loci[locus];
+        const unsigned    nContigs = (lo.status == ASM_OK) ? lo.n_contigs : 0u;
+        // slots without a contig: one lane each
+        if (lane >= nContigs && lane < P.max_assembly_count) {
+          SmallSvTaskInfo none = {(lo.status != ASM_OK) ? 1 : 0, 0, 0, -1};
+          P.info[locus * P.max_assembly_count + lane] = none;
+        }
+        for (unsigned ci = 0; ci < nContigs; ++ci) {
+          const unsigned        slot = locus * P.max_assembly_count + ci;
+          const SmallSvTaskInfo info = scheduleSlot(P, slot, ltable, gtable);
+          wv::sync();  // single reconvergence point of every exit of scheduleSlot
+          if (lane == 0) P.info[slot] = info;
+          if (info.bucket >= 0) {
+            const unsigned b = unsigned(info.bucket);
+            if (lane == 0) {
+              const AlignTaskDev& t = P.tasks[slot];
+              const unsigned slabLen = schedSlabLen(P, b, t.query_len, t.ref1_len);
+              pend->slot[b][pend->count[b]] = slot;
+              pend->count[b] += 1;
+              pend->cigarWords += 4 * t.query_len + 16;
+              if (slabLen > pend->maxref[b]) pend->maxref[b] = slabLen;
+            }
+            wv::sync();
+            if (pend->count[b] == SCHED_PEND) schedFlush(P, pend, b, total);
           }
           wv::sync();
-          if (pend->count[b] == SCHED_PEND) schedFlush(P, pend, b, total);
         }
-        wv::sync();
       }
     }
   }

@@ -1266,6 +1266,8 @@ struct LdsContig {
       const unsigned sl  = wv::readlane(candSlotV, c);
       const unsigned nL  = wv::readlane(nLeft, c), nR = wv::readlane(nRight, c), len = nL + k + nR;
       const unsigned seedPb = gp[slotNode[sl]];
+      // (A, C, G, T alone: scheduleEpilogue compiles the 2-bit form of the trim, scheduleContig<false>.  An emitter that copied read bytes
+      // would have to switch it to <true> -- tests/test_glue_edges.py::*non_acgtn* would show the loss on the fused route)
       for (unsigned i = lane; i < len; i += 64) P.seq_arena[so + i] = uint8_t("ACGT"[contigCode(sl, nL, seedPb, i)]);
       {
         // lane h * W + w holds word w of the support (h = 0) / reject (h = 1) set
@@ -1349,7 +1351,7 @@ struct LdsContig {
     for (unsigned f = 0; f < finalCount; ++f) {
       const unsigned        len  = lenAt(f);
       const unsigned        slot = locus * maxAsm + f;
-      const SmallSvTaskInfo info = scheduleContig(S, slot, locus, so, len, ltable, lseq, lseqBytes, nullptr);
+      const SmallSvTaskInfo info = scheduleContig<false>(S, slot, locus, so, len, ltable, lseq, lseqBytes, nullptr);  // (its texts are "ACGT"[code])
       wv::sync();  // single reconvergence point of every exit of scheduleContig
       const int bucket = wv::first(info.bucket);
       if (lane == 0) {

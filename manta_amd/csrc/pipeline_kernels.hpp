@@ -20,7 +20,7 @@ WV_DEV SmallSvTaskInfo scheduleSlot(const ScheduleParams& P, const unsigned slot
     return none;
   }
   const AsmContigOut co = P.contigs[slot];
-  return scheduleContig(P, slot, locus, co.seq_off, co.seq_len, ltable, reinterpret_cast<uint8_t*>(ltable) + SCHED_TABLE_BYTES, SCHED_SEQ_BYTES, gtable);
+  return scheduleContig<true>(P, slot, locus, co.seq_off, co.seq_len, ltable, reinterpret_cast<uint8_t*>(ltable) + SCHED_TABLE_BYTES, SCHED_SEQ_BYTES, gtable);
 }
 
 /// per-wave pending bucket entries (LDS): a bucket's list takes them eight at a time, with one atomic

@@ -3,6 +3,14 @@
 // ONE copy for its two callers: the epilogue of the LDS contig kernels (asm_contig.hpp: the wave that emitted a locus' contigs
 // schedules them at once, in the locus' own LDS share) and smallsv_schedule_kernel (pipeline_kernels.hpp: every locus the epilogue
 // did not take).
+//   The reference's trim is byte-generic: a std::set<std::string> of the contig's 10-mers, looked up with substrings of the window.  So
+// is this one, in two forms of one table.  A contig of A, C, G and T alone -- every contig of the LDS contig kernels, which emit their
+// text from 2-bit codes and hand a pile with any other byte to the general path -- keys the table by the 10-mer's 20-bit code; a window
+// 10-mer with any other byte cannot be in it.  A contig that holds any other byte (a seed word of assemble_generic_kernel: lower case,
+// '=', an IUPAC letter, a byte >= 0x80) keys it by a hash of the 10 bytes, stores the 10-mer's position and compares the bytes on a
+// hit.  ('N' counts as such a byte here: the reference's set holds strings, and a contig 10-mer with an 'N' matches the same window
+// text.)  That form exists in scheduleContig<true> alone, smallsv_schedule_kernel's instance: the epilogue's scheduleContig<false> is
+// the 2-bit form and nothing else, and no locus with such a contig ever reaches it.
 #pragma once
 #include "align_kernels.hpp"
 #include "assemble_kernels.hpp"
@@ -113,6 +121,31 @@ WV_DEV bool merLookup(const uint32_t* table, const unsigned mask, const unsigned
   }
 }
 
+/// the byte-exact form: hash of the 10 bytes at p (the table's key), and their comparison on a hit
+WV_DEV unsigned merHashBytes(const uint8_t* p)
+{
+  unsigned h = 2166136261u;
+  for (int i = 0; i < SMALLSV_MER; ++i) h = (h ^ p[i]) * 16777619u;
+  return h ^ (h >> 15);
+}
+WV_DEV bool merEqualBytes(const uint8_t* a, const uint8_t* b)
+{
+  bool eq = true;
+  for (int i = 0; i < SMALLSV_MER; ++i) eq = eq && (a[i] == b[i]);
+  return eq;
+}
+/// is the 10-mer at window + i one of the contig's?  The table holds 1 + the position in the contig of every distinct 10-mer.
+WV_DEV bool merLookupBytes(const uint32_t* table, const unsigned mask, const uint8_t* contig, const uint8_t* mer)
+{
+  unsigned s = merHashBytes(mer) & mask;
+  while (true) {
+    const uint32_t v = table[s];
+    if (v == 0) return false;
+    if (merEqualBytes(contig + (v - 1), mer)) return true;
+    s = (s + 1) & mask;
+  }
+}
+
 /// columns per lane of bucket b
 WV_DEV unsigned schedE(const ScheduleParams& P, const unsigned b)
 {
@@ -140,10 +173,12 @@ WV_HD bool schedTableFitsLds(const unsigned clen)
 
 /// One contig (record `slot` of `locus`, text at seq_arena + seqOff, clen bases): 10-mer reference trim + alignment task set-up.
 /// `ltable`: SCHED_TABLE_BYTES of LDS, `lseq`: lseqBytes of LDS for the staged texts (16-byte aligned), `gtable`: P.table_cap words
-/// of memory for the table of a contig beyond 512 bases (nullptr: the caller has checked schedTableFitsLds).  Returns the slot's
+/// of memory for the table of a contig beyond 512 bases (nullptr: the caller has checked schedTableFitsLds).  BYTES: the caller's
+/// contigs may hold bytes outside ACGT (the header comment; false: the 2-bit form alone is compiled).  Returns the slot's
 /// SmallSvTaskInfo; every exit is wave-uniform and the caller stores the record after a single reconvergence point.  (An earlier
 /// form that stored from lane 0 and `continue`d straight to the work-queue pop was compiled into a loop whose lanes left at
 /// different times -- 63 lanes then re-ran the pop's readfirstlane without lane 0 and spun forever on loci without contigs.)
+template <bool BYTES>
 WV_DEV SmallSvTaskInfo scheduleContig(const ScheduleParams& P, const unsigned slot, const unsigned locus, const uint64_t seqOff, const unsigned clen,
                                       uint32_t* ltable, uint8_t* lseq, const unsigned lseqBytes, uint32_t* gtable)
 {
@@ -184,8 +219,25 @@ WV_DEV SmallSvTaskInfo scheduleContig(const ScheduleParams& P, const unsigned sl
   const unsigned mask  = tcap - 1;
   uint32_t*      table = (tcap * 4 <= SCHED_TABLE_BYTES) ? ltable : gtable;
   for (unsigned i = lane; i < tcap; i += 64) table[i] = 0;
+  // (wave-uniform) a byte outside ACGT in the contig: the table is keyed by the bytes
+  bool exact = false;
+  if (BYTES) {
+    bool other = false;
+    for (unsigned i = lane; i < clen; i += 64) other = other || (baseCode(contig[i]) > 3);
+    exact = wv::any(other);
+  }
   wv::sync();
-  for (int p0 = 0; p0 + SMALLSV_MER <= int(clen); p0 += MER_BATCH) {
+  if (BYTES && exact) {
+    for (unsigned p = lane; p + SMALLSV_MER <= clen; p += 64) {
+      unsigned s = merHashBytes(contig + p) & mask;
+      while (true) {
+        const uint32_t old = wv::atomic_cas(&table[s], 0u, p + 1);
+        if (old == 0 || merEqualBytes(contig + (old - 1), contig + p)) break;
+        s = (s + 1) & mask;
+      }
+    }
+  }
+  for (int p0 = 0; !exact && p0 + SMALLSV_MER <= int(clen); p0 += MER_BATCH) {
     bool           valid;
     const unsigned code = merCodes55(contig, int(clen), p0, valid);
     if (!valid) continue;
@@ -218,8 +270,16 @@ WV_DEV SmallSvTaskInfo scheduleContig(const ScheduleParams& P, const unsigned sl
       bool           vf, vb;
       const unsigned codeF = merCodesFromBase(cf, vf), codeB = merCodesFromBase(cb, vb);
       const int      iF = fBase + int(lane), iB = bBase + int(lane);
-      const bool     hitF = !fDone && vf && iF <= maxFwdRefIndex && merLookup(table, mask, codeF);
-      const bool     hitB = !bDone && vb && iB >= minRevRefIndex && iB <= bTop && merLookup(table, mask, codeB);
+      bool           hitF, hitB;
+      if (BYTES && exact) {  // (the codes above go unused: a window 10-mer is looked up by its bytes)
+        const bool inF = lane < unsigned(MER_BATCH) && iF >= 0 && iF + SMALLSV_MER <= refSize;
+        const bool inB = lane < unsigned(MER_BATCH) && iB >= 0 && iB + SMALLSV_MER <= refSize;
+        hitF = !fDone && inF && iF <= maxFwdRefIndex && merLookupBytes(table, mask, contig, ref + iF);
+        hitB = !bDone && inB && iB >= minRevRefIndex && iB <= bTop && merLookupBytes(table, mask, contig, ref + iB);
+      } else {
+        hitF = !fDone && vf && iF <= maxFwdRefIndex && merLookup(table, mask, codeF);
+        hitB = !bDone && vb && iB >= minRevRefIndex && iB <= bTop && merLookup(table, mask, codeB);
+      }
       const uint64_t mF = wv::ballot(hitF), mB = wv::ballot(hitB);
       if (!fDone) {
         if (mF) {

@@ -295,6 +295,67 @@ int manta_smallsv_set_qc(manta_smallsv_t* b, const manta_align_scores_t* filter_
 int manta_smallsv_download_qc(manta_smallsv_t* b, manta_smallsv_qc_t* qc, uint64_t cap, uint32_t* seg_arena, uint64_t seg_cap,
                               uint64_t* seg_used);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Small-SV large-insertion search: what the refiner does on an isolated complex edge (isFindLargeInsertions) to find insertions too
+ * long to assemble through
+ *   the per-contig edge test                            SVCandidateAssemblyRefiner.cpp:2079-2117, with isLargeInsertAlignment (:611-639),
+ *   isLargeInsertSegment (:563-608) and apath_limit_read_length (blt_util/align_path.cpp:295-329) on contig.conservativeRange;
+ *   processLargeInsertion                               :833-1007 up to the candidate itself: the left/right pair (:850-915), the fake
+ *   contig left + 100 x 'N' + right aligned with GlobalAligner(largeInsertCompleteAlignScores) against the window between the
+ *   UNADJUSTED cuts (:917-938), getLargestInsertSegment (:230-279), isFinishedLargeInsertAlignment (:642-665), getInsertTrim
+ *   (:802-830) and the two 40-base flank tests (:962-974).
+ * What needs the SVCandidate stays with the caller: setSmallCandSV, the exclusion of positions that already carry an insertion and the
+ * two unknownSizeInsertion sequences (left contig from trim_begin; right contig up to trim_end - (left length + 100)).
+ * Limits: at most 64 contigs per locus and contigs below 2^28 bases, else MANTA_E_UNSUPPORTED in the locus' record; a path whose read
+ * length differs from its contig's gets MANTA_E_INVALID_ARG in the contig's record.  A locus one of whose contig alignments failed
+ * carries that status and is not searched.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t  status;       /* MANTA_OK or MANTA_E_* for this contig; a failed alignment's status is carried over */
+  uint32_t is_candidate; /* the contig enters largeInsertionCandidateIndex; every field below is 0 when it does not
+                            (the reference's cleared LargeInsertionInfo) */
+  uint32_t is_left, is_right;         /* LargeInsertionInfo::isLeftCandidate / isRightCandidate, of the conservative path */
+  uint32_t contig_offset, ref_offset; /* ... ::contigOffset / refOffset, of the full path (:2104-2105) */
+  int32_t  score;                     /* ... ::score, of the conservative path */
+  uint32_t reserved;
+} manta_large_insert_edge_t;
+
+typedef struct {
+  int32_t  status;   /* MANTA_OK or MANTA_E_* for this locus; MANTA_E_EMPTY_SEQ: a pair was found and the cut window is empty */
+  uint32_t has_pair; /* processLargeInsertion's isLargeInsertionPair; everything below is 0 without one */
+  uint32_t left_contig, right_contig; /* leftIndex / rightIndex: contigs of the locus, 0-based */
+  int32_t  break_dist, break_score;   /* of the chosen pair */
+  uint32_t n_insert_segments;         /* what getLargestInsertSegment(path, 100) returns: 0 or 1 */
+  uint32_t seg_first, seg_last;       /* that segment, indices into the fake alignment's path */
+  uint32_t is_finished;               /* isFinishedLargeInsertAlignment */
+  int32_t  trim_begin, trim_end;      /* getInsertTrim; 0 unless is_finished */
+  uint32_t is_flank_ok;               /* both flank tests pass: the reference goes on to setSmallCandSV */
+  uint32_t reserved;
+  manta_align_result_t align; /* the fake contig's alignment; begin_pos1 already includes leading_cut (:940) */
+} manta_large_insertion_t;
+
+/* The data arguments are exactly what manta_smallsv_download / manta_smallsv_batch return (loci, contigs, alignments, seq_arena,
+ * cigar_arena) and what they were given (refs, ref_off, cuts).  edge_scores / complete_scores: SVRefinerOptions::
+ * largeInsertEdgeAlignScores / largeInsertCompleteAlignScores.  edge_out[i] belongs to contigs[i] (records of contigs no locus refers to
+ * are zeroed), li_out[l] to loci[l].  cigar_cap / *cigar_used count u32 words; 2 * (left + right + 100) + 8 per locus always suffice.
+ * Per-item failures do not stop the batch: the call returns such an item's code and every other record is valid.  A failure of the
+ * call itself (bad arguments, cigar arena too small, device error) writes no record at all.  The same holds for
+ * manta_smallsv_download_large_insertion. */
+int manta_smallsv_large_insertion_batch(
+    manta_ctx_t* ctx, const manta_align_scores_t* edge_scores, const manta_align_scores_t* complete_scores, uint32_t n_loci,
+    const manta_asm_locus_result_t* loci, const manta_asm_contig_t* contigs, const manta_smallsv_alignment_t* alignments,
+    const uint8_t* seq_arena, const uint32_t* cigar_arena, const uint8_t* refs, const uint64_t* ref_off, const manta_ref_cuts_t* cuts,
+    manta_large_insert_edge_t* edge_out, manta_large_insertion_t* li_out, uint32_t* cigar_out, uint64_t cigar_cap, uint64_t* cigar_used);
+
+/* Staged pipeline, opt-in: with the stage set, manta_smallsv_run launches the search behind the aligners (and QC) on data that never
+ * left the device; manta_smallsv_download_large_insertion returns records index-aligned with the contigs[] and loci[] of
+ * manta_smallsv_download (edge_cap / li_cap: records the caller's arrays hold).  edge_scores == NULL switches the stage off again.
+ * Without the call nothing about run / stats / output_sizes / download changes. */
+int manta_smallsv_set_large_insertion(manta_smallsv_t* b, const manta_align_scores_t* edge_scores, const manta_align_scores_t* complete_scores);
+int manta_smallsv_download_large_insertion(manta_smallsv_t* b, manta_large_insert_edge_t* edge_out, uint64_t edge_cap,
+                                           manta_large_insertion_t* li_out, uint64_t li_cap, uint32_t* cigar_out, uint64_t cigar_cap,
+                                           uint64_t* cigar_used);
+
 /* getQuerySeqMatchCount (SVCandidateAssemblyRefiner.cpp:393-418) by itself: counts[i] = number of placements of the query in the
  * target with float(mismatches) / float(query_len) <= max_mismatch_rate, exactly as the reference's float test decides it (a query
  * 'N' always mismatches; query_len == 0 or query_len > target_len: 0).  Any target length, any rate; query_len < 2^32 - 1. */

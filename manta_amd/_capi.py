@@ -96,6 +96,20 @@ class SmallSvQc(ctypes.Structure):
                 ("seg_off", ctypes.c_uint64)]
 
 
+class LargeInsertEdge(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32)] + [(n, ctypes.c_uint32) for n in ("is_candidate", "is_left", "is_right", "contig_offset",
+                                                                            "ref_offset")] + [("score", ctypes.c_int32),
+                                                                                              ("reserved", ctypes.c_uint32)]
+
+
+class LargeInsertion(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("has_pair", ctypes.c_uint32), ("left_contig", ctypes.c_uint32), ("right_contig", ctypes.c_uint32),
+                ("break_dist", ctypes.c_int32), ("break_score", ctypes.c_int32), ("n_insert_segments", ctypes.c_uint32),
+                ("seg_first", ctypes.c_uint32), ("seg_last", ctypes.c_uint32), ("is_finished", ctypes.c_uint32),
+                ("trim_begin", ctypes.c_int32), ("trim_end", ctypes.c_int32), ("is_flank_ok", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("align", AlignResult)]
+
+
 class SeqMatchTask(ctypes.Structure):
     _fields_ = [("target_off", ctypes.c_uint64), ("query_off", ctypes.c_uint64), ("target_len", ctypes.c_uint32),
                 ("query_len", ctypes.c_uint32), ("max_mismatch_rate", ctypes.c_float), ("reserved", ctypes.c_uint32)]
@@ -120,6 +134,31 @@ def _decode_qc(records, n, segs):
                 at += q.span_n_segments[s]
         out.append(d)
     return out
+
+
+LI_EDGE_FIELDS = ("status", "is_candidate", "is_left", "is_right", "contig_offset", "ref_offset", "score")
+LI_FIELDS = ("status", "has_pair", "left_contig", "right_contig", "break_dist", "break_score", "n_insert_segments", "seg_first", "seg_last",
+             "is_finished", "trim_begin", "trim_end", "is_flank_ok")
+
+
+def _decode_li(edges, n_edges, recs, n_loci, cig):
+    """manta_large_insert_edge_t / manta_large_insertion_t records + cigar arena -> (one dict per contig, one dict per locus); a locus'
+    dict carries the fake alignment as `score`, `begin` and `cigar` (text) where there is one"""
+    e_out = [{k: int(getattr(edges[i], k)) for k in LI_EDGE_FIELDS} for i in range(n_edges)]
+    l_out = []
+    for l in range(n_loci):
+        r = recs[l]
+        d = {k: int(getattr(r, k)) for k in LI_FIELDS}
+        a = r.align
+        d.update(score=int(a.score), begin=int(a.begin_pos1), cigar=cigar_string(cig[int(a.cigar1_off):int(a.cigar1_off) + int(a.cigar1_len)]))
+        l_out.append(d)
+    return e_out, l_out
+
+
+def _li_check(lib, rc, edges, n_edges, recs, n_loci, strict):
+    """per-item codes are in the records; a code no record carries is the call's own failure"""
+    carried = {edges[i].status for i in range(n_edges)} | {recs[l].status for l in range(n_loci)}
+    lib._check(rc, allow=() if strict else tuple(c for c in carried if c != 0))
 
 
 def _qc_check(lib, rc, records, n, strict):
@@ -287,6 +326,63 @@ class Lib:
         arr = lambda v, t: np.array(v + [0], dtype=t)
         return self.smallsv_qc_raw(filter_scores, min_indel, loci, contigs, aligns, arr(seq, np.uint8), arr(cig, np.uint32), arr(refs, np.uint8),
                                    np.array(ref_off, dtype=np.uint64), strict=strict)[:n]
+
+    # ------------------------------------------------------------------ small-SV large-insertion search
+    def smallsv_large_insertion_raw(self, edge_scores, complete_scores, loci, contigs, aligns, seq, cig, refs, ref_off, cuts, strict=False):
+        """manta_smallsv_large_insertion_batch on records / arenas laid out as manta_smallsv_download returns them; cuts: int32 array
+        (n_loci, 4) -> (one dict per contig record, one dict per locus) (see _decode_li)"""
+        n_loci = len(loci)
+        n = 0
+        words = 8 * max(n_loci, 1)
+        for r in loci:
+            if r.status == 0 and r.n_contigs:
+                n = max(n, r.first_contig + r.n_contigs)
+                lens = sorted(contigs[r.first_contig + c].seq_len for c in range(r.n_contigs))
+                words += 2 * (sum(lens[-2:]) + 100)
+        edges, recs = (LargeInsertEdge * max(n, 1))(), (LargeInsertion * max(n_loci, 1))()
+        out = np.zeros(words, dtype=np.uint32)
+        used = ctypes.c_uint64(0)
+        es, cs = AlignScores(*edge_scores), AlignScores(*complete_scores)
+        f = self.lib.manta_smallsv_large_insertion_batch
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 11 + [ctypes.c_uint64, ctypes.c_void_p]
+        rc = f(self.ctx, ctypes.byref(es), ctypes.byref(cs), n_loci, loci, contigs, aligns, _p(seq), _p(cig), _p(refs), _p(ref_off), _p(cuts),
+               edges, recs, _p(out), ctypes.c_uint64(len(out)), ctypes.byref(used))
+        _li_check(self, rc, edges, n, recs, n_loci, strict)
+        return _decode_li(edges, n, recs, n_loci, out)
+
+    def smallsv_large_insertion_batch(self, edge_scores, complete_scores, loci_items, strict=False):
+        """loci_items: per locus (reference window, leading cut, trailing cut, [contig, ...]) with every contig a dict of `seq`, `begin`,
+        `cigar` (text), `cons` (begin, end) and optionally `status` (of its alignment) -> (per locus a list of edge dicts, one dict per
+        locus)"""
+        n_loci = len(loci_items)
+        n = sum(len(it[3]) for it in loci_items)
+        loci, contigs, aligns = (AsmLocusResult * max(n_loci, 1))(), (AsmContig * max(n, 1))(), (SmallSvAlignment * max(n, 1))()
+        seq, cig, refs, ref_off, cuts = bytearray(), [], bytearray(), [0], []
+        i = 0
+        for l, (ref, lead, trail, items) in enumerate(loci_items):
+            loci[l].n_contigs, loci[l].first_contig = len(items), i
+            for c in items:
+                words, cb = pack_cigar(c["cigar"]), _b(c["seq"])
+                contigs[i].seq_off, contigs[i].seq_len = len(seq), len(cb)
+                contigs[i].conservative_begin, contigs[i].conservative_end = c["cons"]
+                aligns[i].align.status = c.get("status", 0)
+                aligns[i].align.begin_pos1 = c["begin"]
+                aligns[i].align.cigar1_off, aligns[i].align.cigar1_len = len(cig), len(words)
+                seq += cb
+                cig += words
+                i += 1
+            refs += _b(ref)
+            ref_off.append(len(refs))
+            cuts.append([lead, trail, 0, 0])
+        e, r = self.smallsv_large_insertion_raw(
+            edge_scores, complete_scores, loci, contigs, aligns, np.frombuffer(bytes(seq) + b"\0", dtype=np.uint8),
+            np.array(cig + [0], dtype=np.uint32), np.frombuffer(bytes(refs) + b"\0", dtype=np.uint8), np.array(ref_off, dtype=np.uint64),
+            np.ascontiguousarray(np.array(cuts + [[0, 0, 0, 0]], dtype=np.int32)), strict=strict)
+        per_locus, i = [], 0
+        for it in loci_items:
+            per_locus.append(e[i:i + len(it[3])])
+            i += len(it[3])
+        return per_locus, r[:n_loci]
 
     def seq_match_count_batch(self, tasks):
         """tasks: (target, query, max mismatch rate) -> getQuerySeqMatchCount of each"""
@@ -669,6 +765,35 @@ class SmallSvBatch:
         rc = f(self.h, qc, ctypes.c_uint64(cap), _p(segs), ctypes.c_uint64(len(segs) // 2), ctypes.byref(used))
         _qc_check(self.lib, rc, qc, cap, strict)
         return _decode_qc(qc, cap, segs)
+
+
+def _set_large_insertion(self, edge_scores, complete_scores=None):
+    """large-insertion search behind the aligners of every later run (edge_scores None: off again)"""
+    f = self.lib.lib.manta_smallsv_set_large_insertion
+    f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    es = AlignScores(*edge_scores) if edge_scores is not None else None
+    cs = AlignScores(*complete_scores) if complete_scores is not None else None
+    self.lib._check(f(self.h, ctypes.byref(es) if es is not None else None, ctypes.byref(cs) if cs is not None else None))
+
+
+def _download_large_insertion(self, strict=False):
+    """records of the last run, index-aligned with the contig and locus records of download() -> (one dict per contig, one per locus)"""
+    sizes = [ctypes.c_uint64(0) for _ in range(4)]
+    self.lib._check(self.lib.lib.manta_smallsv_output_sizes(self.h, *[ctypes.byref(x) for x in sizes]))
+    cap, n_loci = max(1, int(sizes[0].value)), self.n_loci
+    edges, recs = (LargeInsertEdge * cap)(), (LargeInsertion * max(n_loci, 1))()
+    out = np.zeros(2 * int(sizes[1].value) + 208 * max(n_loci, 1), dtype=np.uint32)  # (two contigs of a locus + 100, twice, + 8)
+    used = ctypes.c_uint64(0)
+    f = self.lib.lib.manta_smallsv_download_large_insertion
+    f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                  ctypes.c_void_p]
+    rc = f(self.h, edges, ctypes.c_uint64(cap), recs, ctypes.c_uint64(max(n_loci, 1)), _p(out), ctypes.c_uint64(len(out)), ctypes.byref(used))
+    _li_check(self.lib, rc, edges, cap, recs, n_loci, strict)
+    return _decode_li(edges, cap, recs, n_loci, out)
+
+
+SmallSvBatch.set_large_insertion = _set_large_insertion
+SmallSvBatch.download_large_insertion = _download_large_insertion
 
 
 def small_sv_text(d):

@@ -995,6 +995,11 @@ int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates)
       smallsvQcLaunch(b);
       stage("qc");
     }
+    b->liRan = false;
+    if (b->liOn) {  // large-insertion search on the same data (manta_smallsv_set_large_insertion); outside the timed stages
+      smallsvLiLaunch(b);
+      stage("large-insertion");
+    }
     b->ran = true;
     return MANTA_OK;
   } catch (const std::exception& e) {

@@ -30,6 +30,7 @@
 #include "split_kernels.hpp"
 #include "read_class_kernels.hpp"
 #include "smallsv_qc_kernels.hpp"
+#include "smallsv_li_kernels.hpp"
 #include <unordered_map>
 #include "rt.hpp"
 #include "host_pool.hpp"
@@ -119,6 +120,7 @@ struct manta_ctx {
   DevBuf dSplitTasks, dSplitResults, dSplitTables;
   DevBuf dRc[16];  // manta_read_piles_batch: inputs, workspace, outputs
   DevBuf dQc[6];   // manta_smallsv_qc_batch / manta_seq_match_count_batch: tasks, records, segments, counters, references, texts
+  DevBuf dLi[14];  // manta_smallsv_large_insertion_batch: inputs (tasks, loci, texts, paths, references) and the stage's buffers (LiBufs)
   rt::Stream stream;  // the context's own stream (manta_align_batch / manta_assemble_batch run on it)
   int        deviceId = 0;
   // worker pipelines of the whole-batch calls (manta_smallsv_batch / manta_spanning_batch), kept across calls
@@ -1661,6 +1663,11 @@ struct manta_smallsv : PipeBase {
   manta_align_scores_t  qcScores{};
   uint32_t              qcMinIndel = 0;
   DevBuf                dQc, dQcSegs, dQcCnt;
+  // large-insertion search behind the aligners and QC (manta_smallsv_set_large_insertion; off unless asked for)
+  bool                  liOn = false, liRan = false;
+  manta_align_scores_t  liEdgeScores{}, liCompleteScores{};
+  DevBuf                dLi[9];  // the stage's buffers (LI_BUF_*)
+  manta_dev::LiParams   liParams{};  // of the last run with the stage set: where its records are
   using PipeBase::PipeBase;
 };
 
@@ -1823,6 +1830,224 @@ int qcCompact(manta_ctx_t* ctx, uint64_t n, RecordOf recordOf, const uint32_t* h
   if (seg_used) *seg_used = used;
   if (worst != MANTA_OK) return fail(ctx, worst, std::string(who) + ": one or more contigs failed; see per-item status");
   return MANTA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// large-insertion search (smallsv_li_kernels.hpp)
+// ------------------------------------------------------------------------------------------------------
+/// the stage's own device buffers, `LiParams` outputs in this order
+enum { LI_BUF_EDGES = 0, LI_BUF_RECS, LI_BUF_TASKS, LI_BUF_RESULTS, LI_BUF_CIGAR, LI_BUF_FAKE, LI_BUF_BUCKETS, LI_BUF_COUNTS, LI_BUF_SLABS, LI_BUF_COUNT };
+
+inline LiScores liScoresOf(const manta_align_scores_t& sc)
+{
+  return LiScores{sc.match, sc.mismatch, sc.open, sc.extend, sc.off_edge};
+}
+
+/// Edge test, pairing, the completion alignments and the finish on the inputs `L` names (the stand-alone call's staged records or a
+/// pipeline's own state); the caller holds the stream.  The bucket counts are read back once to size the aligner launches.
+/// nEdges: records of L.edges; maxContigLen bounds a contig of the batch (arena sizes).  Returns when the records are on the device.
+inline void liLaunch(manta_ctx_t* ctx, LiParams& L, const uint64_t nEdges, const uint64_t maxContigLen, const manta_align_scores_t& complete, DevBuf* B)
+{
+  for (int k = 0; k < kNumESet; ++k)
+    if (int(liBucketOf(64u * unsigned(kESet[k]))) != k || int(liBucketE(unsigned(k))) != kESet[k]) throw rt::Error("internal: liBucketOf disagrees with the E set");
+  const uint64_t nUnits = L.n_units;
+  // one fake contig per locus at most; pairs are rare, so the arenas stop growing at a budget and a pair beyond it is that locus'
+  // MANTA_E_CAPACITY (the host functions take it)
+  const uint64_t oneFake  = (2 * maxContigLen + LI_MIDDLE + 15) & ~uint64_t(15), oneCigar = 4 * (2 * maxContigLen + LI_MIDDLE) + 16;
+  const uint64_t fakeCap  = std::max<uint64_t>(oneFake, std::min<uint64_t>(nUnits * oneFake, uint64_t(64) << 20));
+  const uint64_t cigarCap = std::min<uint64_t>(std::max<uint64_t>(oneCigar, std::min<uint64_t>(nUnits * oneCigar, uint64_t(32) << 20)), 0xfffffff0ull);
+  L.edges        = B[LI_BUF_EDGES].as<LiEdgeDev>(nEdges + 1);
+  L.recs         = B[LI_BUF_RECS].as<LiRecordDev>(nUnits);
+  L.li_tasks     = B[LI_BUF_TASKS].as<AlignTaskDev>(nUnits);
+  L.li_results   = B[LI_BUF_RESULTS].as<AlignResultDev>(nUnits);
+  L.li_cigar     = B[LI_BUF_CIGAR].as<uint32_t>(cigarCap + 16);
+  L.li_cigar_cap = cigarCap;
+  L.fake         = B[LI_BUF_FAKE].as<uint8_t>(fakeCap + 16);
+  L.fake_cap     = fakeCap;
+  L.bucket_ids   = B[LI_BUF_BUCKETS].as<uint32_t>(uint64_t(kNumESet) * nUnits);
+  L.counts       = B[LI_BUF_COUNTS].as<uint32_t>(LI_CNT_WORDS);
+  rt::dzero(L.counts, sizeof(uint32_t) * LI_CNT_WORDS);
+  rt::dzero(L.li_results, sizeof(AlignResultDev) * nUnits);
+  const int grid = qcGrid(ctx, nUnits);
+  rt::launch(smallsv_li_edge_kernel, grid, 0, L);
+  rt::launch(smallsv_li_pair_kernel, grid, 0, L);
+  uint32_t h[LI_CNT_WORDS];
+  rt::d2h(h, L.counts, sizeof(h));
+  struct Launch {
+    int      k, grid;
+    uint64_t stride;
+  };
+  std::vector<Launch> launches;
+  const int           maxWaves = std::max(1, ctx->cuCount * alignWavesPerCu());
+  const size_t        wsBudget = workspaceBudget(size_t(8) << 30);
+  uint64_t            slabBytes = 0;
+  for (int k = kNumESet - 1; k >= 0; --k) {  // widest first
+    const uint32_t cnt = h[LI_CNT_BUCKET + k];
+    if (cnt == 0) continue;
+    const uint64_t stride = (alignPtrSlabBytes(MANTA_ALIGNER_GLOBAL, kESet[k], h[LI_CNT_MAXREF + k]) + 255) & ~uint64_t(255);
+    int            g      = int(std::min<size_t>(cnt, size_t(maxWaves)));
+    g                     = rt::roundGrid(int(std::max<size_t>(1, std::min<size_t>(size_t(g), wsBudget / stride))));
+    launches.push_back(Launch{k, g, stride});
+    slabBytes = std::max(slabBytes, stride * uint64_t(g));
+  }
+  if (!launches.empty()) {
+    uint8_t* dWs = B[LI_BUF_SLABS].as<uint8_t>(slabBytes + 256);  // (the buckets run one behind the other on this stream and share it)
+    for (const Launch& l : launches) {
+      AlignParams P;
+      P.tasks          = L.li_tasks;
+      P.results        = L.li_results;
+      P.cigar          = L.li_cigar;
+      P.task_ids       = L.bucket_ids + uint64_t(l.k) * nUnits;
+      P.n_tasks        = h[LI_CNT_BUCKET + l.k];
+      P.n_tasks_dev    = nullptr;
+      P.counter        = L.counts + LI_CNT_ALIGN_QUEUE + l.k;
+      P.ptr_ws         = dWs;
+      P.ptr_ws_stride  = l.stride;
+      P.match          = complete.match;
+      P.mismatch       = complete.mismatch;
+      P.open           = complete.open;
+      P.extend         = complete.extend;
+      P.off_edge       = complete.off_edge;
+      P.allow_edge_ins = complete.is_allow_edge_insertion ? 1 : 0;
+      P.extra          = 0;
+      launchAlignKind(MANTA_ALIGNER_GLOBAL, l.k, l.grid, P);
+    }
+    rt::launch(smallsv_li_finish_kernel, grid, 0, L);
+  }
+  rt::sync();
+}
+
+/// what liCompact reads: the stage's records on the host
+struct LiHost {
+  std::vector<LiEdgeDev>      edges;
+  std::vector<LiRecordDev>    recs;
+  std::vector<AlignTaskDev>   tasks;
+  std::vector<AlignResultDev> results;
+  std::vector<uint32_t>       cigar;
+  void fetch(const LiParams& L, const uint64_t nEdges)
+  {
+    uint32_t h[LI_CNT_WORDS];
+    rt::d2h(h, L.counts, sizeof(h));
+    uint64_t used = 0;
+    std::memcpy(&used, h + LI_CNT_CIGAR_USED, sizeof(used));
+    used = std::min<uint64_t>(used, L.li_cigar_cap);
+    edges.resize(nEdges);
+    recs.resize(L.n_units);
+    tasks.resize(L.n_units);
+    results.resize(L.n_units);
+    cigar.resize(used + 1);
+    rt::d2hAsync(edges.data(), L.edges, sizeof(LiEdgeDev) * nEdges);
+    rt::d2hAsync(recs.data(), L.recs, sizeof(LiRecordDev) * L.n_units);
+    rt::d2hAsync(tasks.data(), L.li_tasks, sizeof(AlignTaskDev) * L.n_units);
+    rt::d2hAsync(results.data(), L.li_results, sizeof(AlignResultDev) * L.n_units);
+    rt::d2hAsync(cigar.data(), L.li_cigar, sizeof(uint32_t) * used);
+    rt::sync();
+  }
+};
+
+/// device records -> the caller's records and cigar arena.  edgeOf(i): index of output contig i's device record, or -1 (zeroed);
+/// locusStatus(l): MANTA_OK, or the code of a locus the stage did not look at.  A failure of the call as a whole is found before the
+/// first record is written.
+template <typename EdgeOf, typename LocusStatus>
+int liCompact(manta_ctx_t* ctx, const LiHost& H, uint64_t nEdgesOut, EdgeOf edgeOf, LocusStatus locusStatus, manta_large_insert_edge_t* edge_out,
+              manta_large_insertion_t* li_out, uint32_t* cigar_out, uint64_t cigar_cap, uint64_t* cigar_used, const char* who)
+{
+  const uint64_t nLoci = H.recs.size();
+  auto aligned = [&](uint64_t l) { return locusStatus(l) == MANTA_OK && H.recs[l].status == MANTA_OK && H.recs[l].has_pair != 0; };
+  uint64_t total = 0;
+  for (uint64_t l = 0; l < nLoci; ++l) {
+    if (!aligned(l)) continue;
+    if (uint64_t(H.tasks[l].cigar_off) + H.results[l].cigar1_len >= H.cigar.size())
+      return fail(ctx, MANTA_E_DEVICE_FAULT, std::string(who) + ": path outside the device arena");
+    total += H.results[l].cigar1_len;
+  }
+  if (total > cigar_cap || (total && !cigar_out)) return fail(ctx, MANTA_E_CAPACITY, std::string(who) + ": cigar arena too small");
+  int worst = MANTA_OK;
+  for (uint64_t i = 0; i < nEdgesOut; ++i) {
+    manta_large_insert_edge_t& o(edge_out[i]);
+    std::memset(&o, 0, sizeof(o));
+    const int64_t at = edgeOf(i);
+    if (at < 0) continue;
+    const LiEdgeDev& d(H.edges[size_t(at)]);
+    o.status = d.status;
+    if (o.status != MANTA_OK) {
+      worst = o.status;
+      continue;
+    }
+    o.is_candidate  = d.is_candidate;
+    o.is_left       = d.is_left;
+    o.is_right      = d.is_right;
+    o.contig_offset = d.contig_offset;
+    o.ref_offset    = d.ref_offset;
+    o.score         = d.score;
+  }
+  uint64_t used = 0;
+  for (uint64_t l = 0; l < nLoci; ++l) {
+    manta_large_insertion_t& o(li_out[l]);
+    std::memset(&o, 0, sizeof(o));
+    const LiRecordDev& d(H.recs[l]);
+    o.status = (locusStatus(l) != MANTA_OK) ? locusStatus(l) : d.status;
+    if (locusStatus(l) == MANTA_OK) {
+      o.has_pair     = d.has_pair;
+      o.left_contig  = d.left;
+      o.right_contig = d.right;
+      o.break_dist   = d.break_dist;
+      o.break_score  = d.break_score;
+    }
+    if (o.status != MANTA_OK) {
+      worst = o.status;
+      continue;
+    }
+    if (!d.has_pair) continue;
+    o.n_insert_segments = d.n_insert_segments;
+    o.seg_first         = d.seg_first;
+    o.seg_last          = d.seg_last;
+    o.is_finished       = d.is_finished;
+    o.trim_begin        = d.trim_begin;
+    o.trim_end          = d.trim_end;
+    o.is_flank_ok       = d.is_flank_ok;
+    const AlignResultDev& r(H.results[l]);
+    o.align.score      = r.score;
+    o.align.is_jumped  = r.is_jumped;
+    o.align.begin_pos1 = d.begin_pos;
+    o.align.cigar1_len = r.cigar1_len;
+    o.align.cigar1_off = used;
+    o.align.cigar2_off = used + r.cigar1_len;
+    std::memcpy(cigar_out + used, H.cigar.data() + H.tasks[l].cigar_off, sizeof(uint32_t) * r.cigar1_len);
+    used += r.cigar1_len;
+  }
+  if (cigar_used) *cigar_used = used;
+  if (worst != MANTA_OK) return fail(ctx, worst, std::string(who) + ": one or more items failed; see per-item status");
+  return MANTA_OK;
+}
+
+/// the search on a finished run's own device state (manta_smallsv_set_large_insertion); the caller holds the pipeline's stream and
+/// has waited for the aligners
+inline void smallsvLiParams(manta_smallsv* b, LiParams& L)
+{
+  std::memset(&L, 0, sizeof(L));
+  L.n_units            = b->nLoci;
+  L.loci               = b->asmStage.dLoci;
+  L.contigs            = b->asmStage.dCont;
+  L.seq_arena          = b->asmStage.dSeq;
+  L.max_assembly_count = b->opt.max_assembly_count;
+  L.refs               = static_cast<const uint8_t*>(b->dRefs.p);
+  L.ref_off            = static_cast<const uint64_t*>(b->dRefOff.p);
+  L.cuts               = static_cast<const SmallSvCuts*>(b->dCuts.p);
+  L.atasks             = static_cast<const AlignTaskDev*>(b->dTasks.p);
+  L.results            = static_cast<const AlignResultDev*>(b->dResults.p);
+  L.info               = static_cast<const SmallSvTaskInfo*>(b->dInfo.p);
+  L.cigar              = static_cast<const uint32_t*>(b->dCigar.p);
+  L.edge               = liScoresOf(b->liEdgeScores);
+  L.complete           = liScoresOf(b->liCompleteScores);
+}
+inline void smallsvLiLaunch(manta_smallsv* b)
+{
+  LiParams L;
+  smallsvLiParams(b, L);
+  liLaunch(b->ctx, L, uint64_t(b->nLoci) * b->opt.max_assembly_count, b->asmStage.maxContigLen, b->liCompleteScores, b->dLi);
+  b->liParams = L;
+  b->liRan    = true;
 }
 
 inline int checkPiles(manta_ctx_t* ctx, const manta_packed_piles_t* pl, const char* who)

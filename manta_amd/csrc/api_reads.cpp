@@ -381,6 +381,146 @@ extern "C" int manta_smallsv_download_qc(manta_smallsv_t* b, manta_smallsv_qc_t*
   }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// small-SV large-insertion search (smallsv_li_kernels.hpp)
+// ------------------------------------------------------------------------------------------------------
+extern "C" int manta_smallsv_large_insertion_batch(
+    manta_ctx_t* ctx, const manta_align_scores_t* edge_scores, const manta_align_scores_t* complete_scores, uint32_t n_loci,
+    const manta_asm_locus_result_t* loci, const manta_asm_contig_t* contigs, const manta_smallsv_alignment_t* alignments,
+    const uint8_t* seq_arena, const uint32_t* cigar_arena, const uint8_t* refs, const uint64_t* ref_off, const manta_ref_cuts_t* cuts,
+    manta_large_insert_edge_t* edge_out, manta_large_insertion_t* li_out, uint32_t* cigar_out, uint64_t cigar_cap, uint64_t* cigar_used)
+{
+  static const char* fn = "manta_smallsv_large_insertion_batch";
+  if (!ctx) return MANTA_E_INVALID_ARG;
+  if (cigar_used) *cigar_used = 0;
+  if (!edge_scores || !complete_scores || (n_loci && (!loci || !ref_off || !cuts || !li_out)))
+    return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": null argument");
+  if (n_loci == 0) return MANTA_OK;
+  // the records the loci refer to, and how much of every arena they reach
+  uint64_t nContigs = 0, seqBytes = 0, cigarWords = 0, maxContigLen = 0;
+  for (uint32_t l = 0; l < n_loci; ++l) {
+    if (ref_off[l + 1] < ref_off[l]) return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": ref_off not monotone");
+    if (loci[l].status != MANTA_OK || loci[l].n_contigs == 0) continue;
+    nContigs = std::max<uint64_t>(nContigs, uint64_t(loci[l].first_contig) + loci[l].n_contigs);
+  }
+  if (nContigs && (!contigs || !alignments || !seq_arena || !cigar_arena || !refs || !edge_out))
+    return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": null argument");
+  std::vector<LiTaskDev>  hTasks(nContigs + 1);
+  std::vector<LiLocusDev> hLoci(n_loci);
+  std::vector<uint8_t>    seen(nContigs + 1, 0);
+  for (uint32_t l = 0; l < n_loci; ++l) {
+    if (loci[l].status != MANTA_OK) continue;
+    for (uint32_t c = 0; c < loci[l].n_contigs; ++c) {
+      const uint64_t i = uint64_t(loci[l].first_contig) + c;
+      if (seen[i]) return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": contig record " + std::to_string(i) + " belongs to two loci");
+      seen[i] = 1;
+      const manta_align_result_t& a(alignments[i].align);
+      seqBytes     = std::max<uint64_t>(seqBytes, contigs[i].seq_off + contigs[i].seq_len);
+      maxContigLen = std::max<uint64_t>(maxContigLen, contigs[i].seq_len);
+      if (a.status == MANTA_OK) cigarWords = std::max<uint64_t>(cigarWords, a.cigar1_off + a.cigar1_len);
+    }
+  }
+  try {
+    rt::setDevice(ctx->deviceId);
+    rt::ScopedStream onStream(ctx->stream);
+    DevBuf* const  B        = ctx->dLi;
+    const uint64_t refBytes = ref_off[n_loci];
+    uint8_t*       dSeq  = B[LI_BUF_COUNT + 0].as<uint8_t>(seqBytes + 16);
+    uint32_t*      dCig  = B[LI_BUF_COUNT + 1].as<uint32_t>(cigarWords + 4);
+    uint8_t*       dRefs = B[LI_BUF_COUNT + 2].as<uint8_t>(refBytes + 16);
+    for (uint32_t l = 0; l < n_loci; ++l) {
+      LiLocusDev& u(hLoci[l]);
+      u.ref          = dRefs + ref_off[l];
+      u.ref_len      = uint32_t(std::min<uint64_t>(ref_off[l + 1] - ref_off[l], 0xffffffffull));
+      u.first        = loci[l].first_contig;
+      u.n            = (loci[l].status == MANTA_OK) ? loci[l].n_contigs : 0u;
+      u.leading_cut  = cuts[l].leading_cut;
+      u.trailing_cut = cuts[l].trailing_cut;
+      u.status       = loci[l].status;
+      for (uint32_t c = 0; c < u.n; ++c) {
+        const uint64_t              i = uint64_t(u.first) + c;
+        const manta_align_result_t& a(alignments[i].align);
+        LiTaskDev&                  t(hTasks[i]);
+        t.contig     = dSeq + contigs[i].seq_off;
+        t.contig_len = contigs[i].seq_len;
+        t.cigar      = dCig + ((a.status == MANTA_OK) ? a.cigar1_off : 0);
+        t.n_cigar    = (a.status == MANTA_OK) ? a.cigar1_len : 0u;
+        t.begin_pos  = a.begin_pos1;
+        t.cons_begin = contigs[i].conservative_begin;
+        t.cons_end   = contigs[i].conservative_end;
+        t.status     = a.status;
+      }
+    }
+    LiParams L;
+    std::memset(&L, 0, sizeof(L));
+    LiTaskDev*  dTasks = B[LI_BUF_COUNT + 3].as<LiTaskDev>(nContigs + 1);
+    LiLocusDev* dLoci  = B[LI_BUF_COUNT + 4].as<LiLocusDev>(n_loci);
+    L.tasks    = dTasks;
+    L.units    = dLoci;
+    L.n_units  = n_loci;
+    L.edge     = liScoresOf(*edge_scores);
+    L.complete = liScoresOf(*complete_scores);
+    rt::h2d(dSeq, seq_arena, seqBytes);
+    rt::h2d(dCig, cigar_arena, 4 * cigarWords);
+    rt::h2d(dRefs, refs, refBytes);
+    rt::h2d(dTasks, hTasks.data(), sizeof(LiTaskDev) * nContigs);
+    rt::h2d(dLoci, hLoci.data(), sizeof(LiLocusDev) * n_loci);
+    liLaunch(ctx, L, nContigs, maxContigLen, *complete_scores, B);
+    LiHost H;
+    H.fetch(L, nContigs);
+    return liCompact(ctx, H, nContigs, [&](uint64_t i) { return seen[i] ? int64_t(i) : int64_t(-1); },
+                     [&](uint64_t) { return int(MANTA_OK); }, edge_out, li_out, cigar_out, cigar_cap, cigar_used, fn);
+  } catch (const std::exception& e) {
+    return fail(ctx, MANTA_E_HIP, e.what());
+  }
+}
+
+extern "C" int manta_smallsv_set_large_insertion(manta_smallsv_t* b, const manta_align_scores_t* edge_scores, const manta_align_scores_t* complete_scores)
+{
+  if (!b) return MANTA_E_INVALID_ARG;
+  if (edge_scores && !complete_scores) return fail(b->ctx, MANTA_E_INVALID_ARG, "manta_smallsv_set_large_insertion: complete_scores is null");
+  b->liOn  = edge_scores != nullptr;
+  b->liRan = false;
+  if (edge_scores) {
+    b->liEdgeScores     = *edge_scores;
+    b->liCompleteScores = *complete_scores;
+  }
+  return MANTA_OK;
+}
+
+extern "C" int manta_smallsv_download_large_insertion(manta_smallsv_t* b, manta_large_insert_edge_t* edge_out, uint64_t edge_cap,
+                                                      manta_large_insertion_t* li_out, uint64_t li_cap, uint32_t* cigar_out, uint64_t cigar_cap,
+                                                      uint64_t* cigar_used)
+{
+  static const char* fn = "manta_smallsv_download_large_insertion";
+  if (!b) return MANTA_E_INVALID_ARG;
+  manta_ctx_t* ctx = b->ctx;
+  if (cigar_used) *cigar_used = 0;
+  if (!b->ran || !b->liRan)
+    return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": no run with the stage set (manta_smallsv_set_large_insertion, then manta_smallsv_run)");
+  try {
+    rt::setDevice(ctx->deviceId);
+    rt::ScopedStream onStream(b->main);
+    const uint32_t nLoci  = b->nLoci, maxAsm = b->opt.max_assembly_count;
+    const uint64_t nSlots = uint64_t(nLoci) * maxAsm;
+    std::vector<AsmLocusOut> hLoci(nLoci);
+    rt::d2h(hLoci.data(), b->asmStage.dLoci, sizeof(AsmLocusOut) * nLoci);
+    LiHost H;
+    H.fetch(b->liParams, nSlots);
+    // contigs[] of manta_smallsv_download: the loci in order, every locus' contigs in order (AsmStage::compact)
+    std::vector<uint64_t> slotOf;
+    for (uint32_t l = 0; l < nLoci; ++l)
+      if (hLoci[l].status == ASM_OK)
+        for (uint32_t c = 0; c < hLoci[l].n_contigs; ++c) slotOf.push_back(uint64_t(l) * maxAsm + c);
+    if (slotOf.size() > edge_cap || (!slotOf.empty() && !edge_out) || nLoci > li_cap || (nLoci && !li_out))
+      return fail(ctx, MANTA_E_CAPACITY, std::string(fn) + ": record array too small");
+    return liCompact(ctx, H, slotOf.size(), [&](uint64_t i) { return int64_t(slotOf[i]); },
+                     [&](uint64_t l) { return asmStatusToAbi(hLoci[l].status); }, edge_out, li_out, cigar_out, cigar_cap, cigar_used, fn);
+  } catch (const std::exception& e) {
+    return fail(ctx, MANTA_E_HIP, e.what());
+  }
+}
+
 extern "C" int manta_seq_match_count_batch(
     manta_ctx_t* ctx, uint32_t n_tasks, const manta_seq_match_task_t* tasks, const uint8_t* seq_arena, uint64_t seq_bytes, uint32_t* counts)
 {

@@ -24,6 +24,7 @@
 #include "split_kernels.hpp"
 #include "read_class_kernels.hpp"
 #include "smallsv_qc_kernels.hpp"
+#include "smallsv_li_kernels.hpp"
 #else
 #error "unknown MANTA_TU"
 #endif

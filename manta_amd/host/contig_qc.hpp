@@ -35,6 +35,16 @@ inline bool qcCallFailed(const int rc, const std::vector<manta_smallsv_qc_t>& qc
     if (q.status == rc) return false;
   return true;
 }
+/// ... and manta_smallsv_large_insertion_batch / manta_smallsv_download_large_insertion, by the same rule
+inline bool liCallFailed(const int rc, const std::vector<manta_large_insert_edge_t>& edges, const std::vector<manta_large_insertion_t>& li)
+{
+  if (rc == MANTA_OK) return false;
+  for (const manta_large_insert_edge_t& e : edges)
+    if (e.status == rc) return false;
+  for (const manta_large_insertion_t& l : li)
+    if (l.status == rc) return false;
+  return true;
+}
 }  // namespace detail
 
 /// one contig alignment of the batch: getSmallSVAssembly's alignment.align, contig.seq and align1RefStr
@@ -101,6 +111,169 @@ inline void findSmallSVCandidateSegmentsBatch(
                            ? 1
                            : 0;
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// large-insertion search (manta_smallsv_large_insertion_batch) over the adapter types
+// ------------------------------------------------------------------------------------------------------
+/// one locus of the batch: its contigs with their GlobalLargeIndelAligner alignments (beginPos in window coordinates), the uncut
+/// reference window and the UNADJUSTED cuts
+struct LargeInsertionLocusInput {
+  const Assembly*               contigs;
+  const std::vector<Alignment>* aligns;
+  const std::string*            refSeq;
+  pos_t                         leadingCut, trailingCut;
+};
+
+/// what processLargeInsertion knows of a locus before it needs the SVCandidate
+struct LargeInsertionLocusResult {
+  std::vector<LargeInsertionInfo> info;       ///< largeInsertInfo, one per contig (cleared for a contig that is no candidate)
+  std::vector<unsigned>           candIndex;  ///< largeInsertionCandidateIndex
+  LargeInsertionPair              pair;
+  AlignmentResult<int>            fakeAlignment;  ///< of left + 100 x 'N' + right, beginPos moved by the leading cut; set with a pair
+  LargeInsertionFinish            finish;
+  int                             deviceStatus = MANTA_OK;  ///< != MANTA_OK: the host functions computed this locus
+};
+
+/// the same on the host: the free functions of refiner_util.hpp plus one GlobalAligner alignment through manta_align_batch
+inline void findLargeInsertionHost(
+    const AlignmentScores<int>& edgeScores, const AlignmentScores<int>& completeScores, const LargeInsertionLocusInput& in,
+    LargeInsertionLocusResult& r, manta_ctx_t* ctx)
+{
+  const unsigned n = unsigned(in.contigs->size());
+  r.info.assign(n, LargeInsertionInfo());
+  r.candIndex.clear();
+  r.pair = LargeInsertionPair();
+  r.fakeAlignment.clear();
+  r.finish = LargeInsertionFinish();
+  std::vector<pos_t> beginPos(n);
+  for (unsigned i = 0; i < n; ++i) {
+    const AssembledContig& c((*in.contigs)[i]);
+    beginPos[i] = (*in.aligns)[i].beginPos;
+    if (isLargeInsertionEdge(edgeScores, (*in.aligns)[i].apath, c.conservativeRange.begin_pos(), c.conservativeRange.end_pos(), r.info[i]))
+      r.candIndex.push_back(i);
+  }
+  r.pair = findLargeInsertionPair(r.candIndex, beginPos, r.info);
+  if (!r.pair.isPair) return;
+  const std::string& left((*in.contigs)[r.pair.leftIndex].seq);
+  const std::string  fake = left + std::string(100, 'N') + (*in.contigs)[r.pair.rightIndex].seq;
+  const std::string  window = in.refSeq->substr(size_t(in.leadingCut), in.refSeq->size() - size_t(in.leadingCut) - size_t(in.trailingCut));
+  const std::string  arena = fake + window;
+  manta_align_task_t task  = manta_align_task_t();
+  task.query_len = uint32_t(fake.size());
+  task.ref1_off  = fake.size();
+  task.ref1_len  = uint32_t(window.size());
+  manta_align_result_t       res = manta_align_result_t();
+  std::vector<uint32_t>      cigar(2 * fake.size() + 8);
+  uint64_t                   used = 0;
+  const manta_align_scores_t sc   = detail::toAbi(completeScores);
+  const int rc = manta_align_batch(ctx, MANTA_ALIGNER_GLOBAL, &sc, 0, 1, &task, reinterpret_cast<const uint8_t*>(arena.data()), arena.size(), &res,
+                                   cigar.data(), cigar.size(), &used);
+  if (rc != MANTA_OK) throw GeneralException("manta_amd large-insertion alignment: " + std::string(manta_last_error(ctx)), rc);
+  r.fakeAlignment.score          = res.score;
+  r.fakeAlignment.isJumped       = res.is_jumped != 0;
+  r.fakeAlignment.align.beginPos = res.begin_pos1 + in.leadingCut;
+  detail::toPath(cigar.data() + res.cigar1_off, res.cigar1_len, r.fakeAlignment.align.apath);
+  r.finish = finishLargeInsertAlignment(completeScores, r.fakeAlignment.align.apath, unsigned(left.size()));
+}
+
+/// The large-insertion search of every locus in ONE device call; a locus with an item the device does not decide (any per-item
+/// status) is recomputed whole by findLargeInsertionHost and carries that status in deviceStatus.
+inline void findLargeInsertionBatch(
+    const AlignmentScores<int>& edgeScores, const AlignmentScores<int>& completeScores, const std::vector<LargeInsertionLocusInput>& items,
+    std::vector<LargeInsertionLocusResult>& results, manta_ctx_t* ctx = nullptr)
+{
+  const size_t n = items.size();
+  results.assign(n, LargeInsertionLocusResult());
+  if (n == 0) return;
+  if (!ctx) ctx = threadContext();
+  std::vector<manta_asm_locus_result_t>  loci(n);
+  std::vector<manta_asm_contig_t>        contigs;
+  std::vector<manta_smallsv_alignment_t> aligns;
+  std::vector<manta_ref_cuts_t>          cuts(n);
+  std::vector<uint8_t>                   seq, refs;
+  std::vector<uint32_t>                  cigar;
+  std::vector<uint64_t>                  refOff(n + 1, 0);
+  uint64_t                               cigarCap = 0;
+  for (size_t l = 0; l < n; ++l) {
+    const LargeInsertionLocusInput& in(items[l]);
+    loci[l]              = manta_asm_locus_result_t();
+    loci[l].n_contigs    = uint32_t(in.contigs->size());
+    loci[l].first_contig = uint32_t(contigs.size());
+    uint64_t total = 0;
+    for (size_t c = 0; c < in.contigs->size(); ++c) {
+      const AssembledContig& ctg((*in.contigs)[c]);
+      manta_asm_contig_t     rec = manta_asm_contig_t();
+      rec.seq_off            = seq.size();
+      rec.seq_len            = uint32_t(ctg.seq.size());
+      rec.conservative_begin = ctg.conservativeRange.begin_pos();
+      rec.conservative_end   = ctg.conservativeRange.end_pos();
+      contigs.push_back(rec);
+      seq.insert(seq.end(), ctg.seq.begin(), ctg.seq.end());
+      total += ctg.seq.size();
+      manta_smallsv_alignment_t a = manta_smallsv_alignment_t();
+      a.align.begin_pos1          = (*in.aligns)[c].beginPos;
+      a.align.cigar1_off          = cigar.size();
+      detail::toPacked((*in.aligns)[c].apath, cigar);
+      a.align.cigar1_len = uint32_t(cigar.size() - a.align.cigar1_off);
+      aligns.push_back(a);
+    }
+    cigarCap += 2 * (total + 100) + 8;
+    refs.insert(refs.end(), in.refSeq->begin(), in.refSeq->end());
+    refOff[l + 1] = refs.size();
+    cuts[l]       = manta_ref_cuts_t{in.leadingCut, in.trailingCut, 0, 0};
+  }
+  seq.push_back(0);
+  refs.push_back(0);
+  cigar.push_back(0);
+  contigs.push_back(manta_asm_contig_t());
+  aligns.push_back(manta_smallsv_alignment_t());
+  std::vector<manta_large_insert_edge_t> edges(contigs.size());
+  std::vector<manta_large_insertion_t>   li(n);
+  std::vector<uint32_t>                  out(cigarCap + 1);
+  uint64_t                               used = 0;
+  const manta_align_scores_t             esc = detail::toAbi(edgeScores), csc = detail::toAbi(completeScores);
+  const int rc = manta_smallsv_large_insertion_batch(ctx, &esc, &csc, uint32_t(n), loci.data(), contigs.data(), aligns.data(), seq.data(), cigar.data(),
+                                                     refs.data(), refOff.data(), cuts.data(), edges.data(), li.data(), out.data(), out.size(), &used);
+  if (detail::liCallFailed(rc, edges, li)) throw GeneralException("manta_amd large-insertion search: " + std::string(manta_last_error(ctx)), rc);
+  for (size_t l = 0; l < n; ++l) {
+    LargeInsertionLocusResult& r(results[l]);
+    const unsigned             count = loci[l].n_contigs;
+    int                        status = li[l].status;
+    for (unsigned c = 0; c < count && status == MANTA_OK; ++c) status = edges[loci[l].first_contig + c].status;
+    if (status != MANTA_OK) {
+      findLargeInsertionHost(edgeScores, completeScores, items[l], r, ctx);
+      r.deviceStatus = status;
+      continue;
+    }
+    r.info.assign(count, LargeInsertionInfo());
+    for (unsigned c = 0; c < count; ++c) {
+      const manta_large_insert_edge_t& e(edges[loci[l].first_contig + c]);
+      if (!e.is_candidate) continue;
+      r.info[c].isLeftCandidate  = e.is_left != 0;
+      r.info[c].isRightCandidate = e.is_right != 0;
+      r.info[c].contigOffset     = e.contig_offset;
+      r.info[c].refOffset        = e.ref_offset;
+      r.info[c].score            = e.score;
+      r.candIndex.push_back(c);
+    }
+    const manta_large_insertion_t& d(li[l]);
+    if (!d.has_pair) continue;
+    r.pair.isPair     = true;
+    r.pair.leftIndex  = d.left_contig;
+    r.pair.rightIndex = d.right_contig;
+    r.pair.breakDist  = d.break_dist;
+    r.pair.breakScore = d.break_score;
+    r.fakeAlignment.clear();
+    r.fakeAlignment.score          = d.align.score;
+    r.fakeAlignment.isJumped       = d.align.is_jumped != 0;
+    r.fakeAlignment.align.beginPos = d.align.begin_pos1;
+    detail::toPath(out.data() + d.align.cigar1_off, d.align.cigar1_len, r.fakeAlignment.align.apath);
+    if (d.n_insert_segments) r.finish.segments.push_back(segment_t(d.seg_first, d.seg_last));
+    r.finish.isFinished = d.is_finished != 0;
+    r.finish.insertTrim.set_range(d.trim_begin, d.trim_end);
+    r.finish.isFlankOK = d.is_flank_ok != 0;
   }
 }
 

@@ -191,60 +191,6 @@ inline void setSmallCandSV(
   if (opt.isOutputContig) sv.contigSeq = contig;
 }
 
-/// blt_util/align_path.cpp:295-329
-inline void apath_limit_read_length(const unsigned target_read_start, const unsigned target_read_end, ALIGNPATH::path_t& apath)
-{
-  bool           isStartSet  = false;
-  unsigned       read_length = 0;
-  const unsigned as          = unsigned(apath.size());
-  unsigned       startSegment = 0, endSegment = as;
-  for (unsigned i = 0; i < as; ++i) {
-    ALIGNPATH::path_segment& ps(apath[i]);
-    if (!ALIGNPATH::is_segment_type_read_length(ps.type)) continue;
-    read_length += ps.length;
-    if (!isStartSet && read_length > target_read_start) {
-      ps.length -= ps.length - (read_length - target_read_start);
-      startSegment = i;
-      isStartSet   = true;
-    }
-    if (read_length >= target_read_end) {
-      if (read_length > target_read_end) ps.length -= (read_length - target_read_end);
-      endSegment = i + 1;
-      break;
-    }
-  }
-  apath = ALIGNPATH::path_t(apath.begin() + startSegment, apath.begin() + endSegment);
-}
-
-/// read-coordinate span of an indel run (:802-830)
-inline known_pos_range2 getInsertTrim(const ALIGNPATH::path_t& apath, const segment_t& segRange)
-{
-  known_pos_range2 range;
-  pos_t            readPos = 0;
-  for (unsigned i = 0; i < apath.size(); ++i) {
-    if (i == segRange.first) range.set_begin_pos(readPos);
-    if (ALIGNPATH::is_segment_type_read_length(apath[i].type)) readPos += pos_t(apath[i].length);
-    if (i == segRange.second) {
-      range.set_end_pos(readPos);
-      return range;
-    }
-  }
-  return range;
-}
-
-/// :642-665
-inline bool isFinishedLargeInsertAlignment(
-    const AlignmentScores<int>& scores, const ALIGNPATH::path_t& apath, const segment_t& insertSegment, const unsigned middleSize)
-{
-  const ALIGNPATH::path_t left(apath.begin(), apath.begin() + insertSegment.second + 1);
-  LargeInsertionInfo      info;
-  info.isLeftCandidate = isLargeInsertSegment(scores, left, info.contigOffset, info.refOffset, info.score, middleSize);
-  ALIGNPATH::path_t rev(apath.begin() + insertSegment.first, apath.end());
-  std::reverse(rev.begin(), rev.end());
-  info.isRightCandidate = isLargeInsertSegment(scores, rev, info.contigOffset, info.refOffset, info.score, middleSize);
-  return info.isLeftCandidate && info.isRightCandidate;
-}
-
 /// the per-locus host glue after a device batch is independent across loci: spread it over host threads
 template <typename F>
 void parallelFor(const size_t n, unsigned threads, F&& body)
@@ -475,6 +421,11 @@ struct SmallSvOutput : AsmOutput {
   // contig QC of the batch (manta_smallsv_qc_batch; only with SVCandidateAssemblyRefiner::setDeviceContigQC): index-aligned with `aligns`
   std::vector<manta_smallsv_qc_t>        qc;
   std::vector<uint32_t>                  qcSegs;
+  // large-insertion search of the batch (manta_smallsv_large_insertion_batch; only with setDeviceLargeInsertion): `liEdges` is
+  // index-aligned with `aligns`, `li` with `loci`
+  std::vector<manta_large_insert_edge_t> liEdges;
+  std::vector<manta_large_insertion_t>   li;
+  std::vector<uint32_t>                  liCigar;
 };
 
 /// what the device contig QC of a batch needs beside the batch's own output
@@ -482,12 +433,17 @@ struct SmallSvQcRequest {
   const AlignmentScores<int>* contigFilterScores;
   unsigned                    minCandidateVariantSize;
 };
+/// ... and the device large-insertion search
+struct SmallSvLiRequest {
+  const AlignmentScores<int>* edgeScores;
+  const AlignmentScores<int>* completeScores;
+};
 
 /// the fused device pipeline for a batch of complex loci
 inline void smallSvBatch(
     manta_ctx_t* ctx, manta_smallsv_t*& b, const IterativeAssemblerOptions& opt, const AlignmentScores<int>& scores, const int largeIndelScore,
     PackedReads& in, const std::vector<const std::string*>& refs, const std::vector<manta_ref_cuts_t>& cuts, SmallSvOutput& out, const unsigned threads,
-    PinnedArena& refStage, const SmallSvQcRequest* qcRequest = nullptr)
+    PinnedArena& refStage, const SmallSvQcRequest* qcRequest = nullptr, const SmallSvLiRequest* liRequest = nullptr)
 {
   if (in.nLoci() == 0) return;
   const manta_asm_options_t  o   = toAbi(opt);
@@ -546,6 +502,34 @@ inline void smallSvBatch(
                                           out.seq.data(), out.cigar.data(), R.bytes, R.off.data(), out.qc.data(), out.qcSegs.data(),
                                           out.qcSegs.size() / 2, &used);
     if (qcCallFailed(rc, out.qc)) check(rc);  // (an item's code is in its record, zeroed above: only the call's own failure is fatal)
+  }
+  if (liRequest) {
+    // likewise one call on the batch's output; a contig or locus the device does not decide keeps its status in the record
+    uint64_t nContigs = 0, cigarCap = 0;
+    for (const manta_asm_locus_result_t& l : out.loci) {
+      if (l.status != MANTA_OK) continue;
+      nContigs = std::max<uint64_t>(nContigs, uint64_t(l.first_contig) + l.n_contigs);
+      uint64_t longest[2] = {0, 0};
+      for (uint32_t c = 0; c < l.n_contigs; ++c) {
+        const uint64_t len = out.contigs[l.first_contig + c].seq_len;
+        if (len > longest[0]) {
+          longest[1] = longest[0];
+          longest[0] = len;
+        } else if (len > longest[1]) {
+          longest[1] = len;
+        }
+      }
+      cigarCap += 2 * (longest[0] + longest[1] + 100) + 8;
+    }
+    out.liEdges.assign(nContigs, manta_large_insert_edge_t());
+    out.li.assign(n, manta_large_insertion_t());
+    if (out.liCigar.size() < cigarCap) out.liCigar.resize(cigarCap);
+    uint64_t                   used = 0;
+    const manta_align_scores_t esc = toAbi(*liRequest->edgeScores), csc = toAbi(*liRequest->completeScores);
+    const int rc = manta_smallsv_large_insertion_batch(ctx, &esc, &csc, n, out.loci.data(), out.contigs.data(), out.aligns.data(), out.seq.data(),
+                                                       out.cigar.data(), R.bytes, R.off.data(), cuts.data(), out.liEdges.data(), out.li.data(),
+                                                       out.liCigar.data(), out.liCigar.size(), &used);
+    if (liCallFailed(rc, out.liEdges, out.li)) check(rc);
   }
 }
 
@@ -644,12 +628,21 @@ struct SVCandidateAssemblyRefiner {
   /// contig QC of the batched small-SV path on the device (default off): one manta_smallsv_qc_batch call on the whole batch's output
   /// replaces the per-contig findSmallSVCandidateSegments; a contig the device does not decide is still computed by that function
   void setDeviceContigQC(const bool on) { _deviceContigQC = on; }
+  /// large-insertion search of the batched small-SV path on the device (default off): with isFindLargeInsertions, one
+  /// manta_smallsv_large_insertion_batch call on the whole batch's output replaces the per-contig edge test, the pairing, the separate
+  /// GlobalAligner batch of the fake contigs and the tests on their alignments; a locus with an item the device does not decide is
+  /// still computed by the host functions.  What needs the SVCandidate (setSmallCandSV, the insertion-position exclusion, the two
+  /// unknown-size sequences) stays on the host.
+  void setDeviceLargeInsertion(const bool on) { _deviceLargeInsertion = on; }
 
   /// work counters of this refiner object (no reference counterpart; for logs and tests)
   struct Stats {
     uint64_t smallLoci = 0, spanningLoci = 0, contigAlignments = 0, realignedContigs = 0, largeInsertionAlignments = 0;
     /// with setDeviceContigQC: contigs whose QC the device decided / that it left to the host function (both stay 0 without)
     uint64_t deviceQCContigs = 0, deviceQCFallbacks = 0;
+    /// with setDeviceLargeInsertion and isFindLargeInsertions: loci whose large-insertion search the device decided / that it left to
+    /// the host functions (both stay 0 without); largeInsertionAlignments counts the fake-contig alignments of either kind
+    uint64_t deviceLargeInsertionLoci = 0, deviceLargeInsertionFallbacks = 0;
   };
   const Stats&        stats() const { return _stats; }
   const RefinerTimes& times() const { return _times; }
@@ -876,6 +869,9 @@ private:
     std::set<pos_t>       insPos;
     AssembledContig       fakeContig;
     detail::AlignJob      job;
+    /// with setDeviceLargeInsertion: the locus' record and the batch's path arena; the alignment and its tests are taken from them
+    const manta_large_insertion_t* device = nullptr;
+    const uint32_t*                deviceCigar = nullptr;
   };
 
   /// frees the read copies of the given plans on half the host threads, in the background (the plans are the batch call's own objects; the
@@ -930,13 +926,15 @@ private:
     _times.pack += tPacked - tStart;
     detail::SmallSvOutput& dev(_smallDev);  // (kept across calls: no re-allocation and zero-fill of tens of MB per batch)
     const detail::SmallSvQcRequest qcRequest{&_opt.refineOpt.contigFilterScores, _opt.scanOpt.minCandidateVariantSize};
+    const detail::SmallSvLiRequest liRequest{&_opt.refineOpt.largeInsertEdgeAlignScores, &_opt.refineOpt.largeInsertCompleteAlignScores};
+    const bool                     isDeviceLI = _deviceLargeInsertion && isFindLargeInsertions;
     detail::smallSvBatch(deviceContext(), _smallPipe, _opt.refineOpt.smallSVAssembleOpt, _opt.refineOpt.largeSVAlignScores, _opt.refineOpt.largeGapOpenScore, packed,
-                         refs, cuts, dev, _hostThreads, _refStage, _deviceContigQC ? &qcRequest : nullptr);
+                         refs, cuts, dev, _hostThreads, _refStage, _deviceContigQC ? &qcRequest : nullptr, isDeviceLI ? &liRequest : nullptr);
     const double tDevice = now();
     _times.device += tDevice - tPacked;
 
     std::vector<std::unique_ptr<LargeInsertionWork>> liWorkByLocus(which.size());
-    std::atomic<uint64_t>                            nContigs(0), nDeviceQC(0), nDeviceQCFallback(0);
+    std::atomic<uint64_t>                            nContigs(0), nDeviceQC(0), nDeviceQCFallback(0), nDeviceLI(0), nDeviceLIFallback(0);
     auto smallLocus = [&](const size_t w) {
       const Plan&              p(plans[which[w]]);
       SVCandidateAssemblyData& data(out[which[w]]);
@@ -950,6 +948,11 @@ private:
       data.extendedContigs.resize(contigCount);
       ContigScoringInfo     rank1Contig, rank2Contig;
       std::vector<unsigned> largeInsertionCandidateIndex;
+      // the device's search of this locus is used whole or not at all: an item it did not decide sends the locus to the host functions
+      bool isLocusDeviceLI = isDeviceLI && dev.li[w].status == MANTA_OK;
+      for (unsigned contigIndex = 0; isLocusDeviceLI && contigIndex < contigCount; ++contigIndex)
+        isLocusDeviceLI = dev.liEdges[dev.loci[w].first_contig + contigIndex].status == MANTA_OK;
+      if (isDeviceLI) ++(isLocusDeviceLI ? nDeviceLI : nDeviceLIFallback);
 
       for (unsigned contigIndex = 0; contigIndex < contigCount; ++contigIndex) {
         const AssembledContig&                 contig(data.contigs[contigIndex]);
@@ -979,17 +982,18 @@ private:
 
         if (isFindLargeInsertions) {  // :2072-2113
           LargeInsertionInfo insertInfo;
-          ALIGNPATH::path_t  apath_conservative(alignment.align.apath);
-          detail::apath_limit_read_length(unsigned(std::max(contig.conservativeRange.begin_pos(), 0)),
-                                          unsigned(std::max(contig.conservativeRange.end_pos(), 0)), apath_conservative);
-          bool isCandidate = isLargeInsertAlignment(_opt.refineOpt.largeInsertEdgeAlignScores, apath_conservative, insertInfo);
-          if (isCandidate) {
-            LargeInsertionInfo insertInfo2;
-            isCandidate = isLargeInsertAlignment(_opt.refineOpt.largeInsertEdgeAlignScores, alignment.align.apath, insertInfo2);
-            if (insertInfo.isLeftCandidate != insertInfo2.isLeftCandidate || insertInfo.isRightCandidate != insertInfo2.isRightCandidate)
-              isCandidate = false;
-            insertInfo.contigOffset = insertInfo2.contigOffset;
-            insertInfo.refOffset    = insertInfo2.refOffset;
+          bool               isCandidate = false;
+          if (isLocusDeviceLI) {
+            const manta_large_insert_edge_t& e(dev.liEdges[dev.loci[w].first_contig + contigIndex]);
+            isCandidate                 = e.is_candidate != 0;
+            insertInfo.isLeftCandidate  = e.is_left != 0;
+            insertInfo.isRightCandidate = e.is_right != 0;
+            insertInfo.contigOffset     = e.contig_offset;
+            insertInfo.refOffset        = e.ref_offset;
+            insertInfo.score            = e.score;
+          } else {
+            isCandidate = isLargeInsertionEdge(_opt.refineOpt.largeInsertEdgeAlignScores, alignment.align.apath, contig.conservativeRange.begin_pos(),
+                                               contig.conservativeRange.end_pos(), insertInfo);
           }
           if (isCandidate) {
             data.largeInsertInfo[contigIndex] = insertInfo;
@@ -1048,6 +1052,10 @@ private:
 
       if (isFindLargeInsertions) {
         std::unique_ptr<LargeInsertionWork> work(new LargeInsertionWork);
+        if (isLocusDeviceLI) {
+          work->device      = &dev.li[w];
+          work->deviceCigar = dev.liCigar.data();
+        }
         if (planLargeInsertion(p, data, largeInsertionCandidateIndex, *work)) {
           work->planIndex = which[w];
           work->insPos    = insPos;
@@ -1066,14 +1074,18 @@ private:
     _stats.contigAlignments += nContigs;
     _stats.deviceQCContigs += nDeviceQC;
     _stats.deviceQCFallbacks += nDeviceQCFallback;
+    _stats.deviceLargeInsertionLoci += nDeviceLI;
+    _stats.deviceLargeInsertionFallbacks += nDeviceLIFallback;
     std::vector<std::unique_ptr<LargeInsertionWork>> liWork;
     for (auto& w : liWorkByLocus)
       if (w) liWork.push_back(std::move(w));
 
     // large-insertion completion: one GlobalAligner batch over every locus that found a left/right pair
+    // (a locus whose search the device did carries its alignment in its record)
     std::vector<detail::AlignJob*> jobs;
-    for (auto& w : liWork) jobs.push_back(&w->job);
-    _stats.largeInsertionAlignments += jobs.size();
+    for (auto& w : liWork)
+      if (!w->device) jobs.push_back(&w->job);
+    _stats.largeInsertionAlignments += liWork.size();
     detail::alignBatch(MANTA_ALIGNER_GLOBAL, _opt.refineOpt.largeInsertCompleteAlignScores, 0, jobs);
     for (auto& w : liWork) finishLargeInsertion(plans[w->planIndex], *w, out[w->planIndex]);
     _times.post += now() - tDevice;
@@ -1083,35 +1095,19 @@ private:
   bool planLargeInsertion(
       const Plan& p, const SVCandidateAssemblyData& data, const std::vector<unsigned>& candIndex, LargeInsertionWork& work) const
   {
-    if (candIndex.empty()) return false;
-    bool             isPair = false;
-    int              bestBreakDist = 0, bestBreakScore = 0;
-    static const int maxBreakDist(35);
-    const unsigned   candCount = unsigned(candIndex.size());
-    for (unsigned c1 = 0; (c1 + 1) < candCount; ++c1) {
-      const unsigned            i1 = candIndex[c1];
-      const Alignment&          align1(data.smallSVAlignments[i1].align);
-      const LargeInsertionInfo& insert1(data.largeInsertInfo[i1]);
-      for (unsigned c2 = c1 + 1; c2 < candCount; ++c2) {
-        const unsigned            i2 = candIndex[c2];
-        const Alignment&          align2(data.smallSVAlignments[i2].align);
-        const LargeInsertionInfo& insert2(data.largeInsertInfo[i2]);
-        if (!((insert1.isLeftCandidate && insert2.isRightCandidate) || (insert2.isLeftCandidate && insert1.isRightCandidate))) continue;
-        const int breakDist = int(std::labs(long(align1.beginPos + pos_t(insert1.refOffset)) - long(align2.beginPos + pos_t(insert2.refOffset))));
-        if (breakDist > maxBreakDist) continue;
-        const int  breakScore = insert1.score + insert2.score;
-        const bool isBetter   = (breakDist < bestBreakDist) || ((breakDist == bestBreakDist) && (breakScore > bestBreakScore));
-        if (!isPair || isBetter) {
-          isPair          = true;
-          work.leftIndex  = i1;
-          work.rightIndex = i2;
-          if (insert1.isRightCandidate) std::swap(work.leftIndex, work.rightIndex);
-          bestBreakDist  = breakDist;
-          bestBreakScore = breakScore;
-        }
-      }
+    if (work.device) {  // the device's pair
+      if (!work.device->has_pair) return false;
+      work.leftIndex  = work.device->left_contig;
+      work.rightIndex = work.device->right_contig;
+    } else {
+      if (candIndex.empty()) return false;
+      std::vector<pos_t> beginPos;
+      for (const AlignmentResult<int>& a : data.smallSVAlignments) beginPos.push_back(a.align.beginPos);
+      const LargeInsertionPair pair = findLargeInsertionPair(candIndex, beginPos, data.largeInsertInfo);
+      if (!pair.isPair) return false;
+      work.leftIndex  = pair.leftIndex;
+      work.rightIndex = pair.rightIndex;
     }
-    if (!isPair) return false;
     static const std::string middle(100, 'N');
     work.fakeContig = data.contigs[work.leftIndex];
     work.fakeContig.seq += (middle + data.contigs[work.rightIndex].seq);
@@ -1135,18 +1131,27 @@ private:
     data.contigs[contigCount] = work.fakeContig;
     AlignmentResult<int>&   fakeAlignment(data.smallSVAlignments[contigCount]);
     std::vector<segment_t>& fakeSegments(data.smallSVSegments[contigCount]);
-    detail::toResult(work.job, fakeAlignment);
-    fakeAlignment.align.beginPos += p.leadingCut;
-    fakeSegments.clear();
-    getLargestInsertSegment(fakeAlignment.align.apath, middleSize, fakeSegments);
-    if (fakeSegments.size() != 1 || fakeSegments[0].second < fakeSegments[0].first) return;
-    if (!detail::isFinishedLargeInsertAlignment(_opt.refineOpt.largeInsertCompleteAlignScores, fakeAlignment.align.apath, fakeSegments[0], middleSize))
-      return;
-    const known_pos_range2 insertTrim(detail::getInsertTrim(fakeAlignment.align.apath, fakeSegments[0]));
-    static const int       minFlankSize(40);  // minSemiLargeInsertionLength, SVCandidateAssemblyRefiner.cpp:558
-    if ((insertTrim.begin_pos() + minFlankSize) > pos_t(leftSeq.size())) return;
-    const pos_t rightOffset = pos_t(leftSeq.size() + middleSize);
-    if ((rightOffset + minFlankSize) > insertTrim.end_pos()) return;
+    LargeInsertionFinish finish;
+    if (work.device) {  // alignment, segment and tests as the device left them in the locus' record (leading cut already added)
+      const manta_large_insertion_t& d(*work.device);
+      fakeAlignment.clear();
+      fakeAlignment.score          = d.align.score;
+      fakeAlignment.isJumped       = d.align.is_jumped != 0;
+      fakeAlignment.align.beginPos = d.align.begin_pos1;
+      detail::toPath(work.deviceCigar + d.align.cigar1_off, d.align.cigar1_len, fakeAlignment.align.apath);
+      if (d.n_insert_segments) finish.segments.push_back(segment_t(d.seg_first, d.seg_last));
+      finish.isFinished = d.is_finished != 0;
+      finish.insertTrim.set_range(d.trim_begin, d.trim_end);
+      finish.isFlankOK = d.is_flank_ok != 0;
+    } else {
+      detail::toResult(work.job, fakeAlignment);
+      fakeAlignment.align.beginPos += p.leadingCut;
+      finish = finishLargeInsertAlignment(_opt.refineOpt.largeInsertCompleteAlignScores, fakeAlignment.align.apath, unsigned(leftSeq.size()), middleSize);
+    }
+    fakeSegments = finish.segments;
+    if (!finish.isFlankOK) return;
+    const known_pos_range2 insertTrim(finish.insertTrim);
+    const pos_t            rightOffset = pos_t(leftSeq.size() + middleSize);
     getExtendedContig(fakeAlignment, work.fakeContig.seq, data.bp1ref.seq(), data.extendedContigs[contigCount]);
     SVCandidate newSV(p.sv);
     newSV.assemblyAlignIndex   = contigCount;
@@ -1314,6 +1319,7 @@ private:
   unsigned                      _planThreads = 1;
   PileDumpWriter*               _pileDump = nullptr;
   bool                          _deviceContigQC = false;
+  bool                          _deviceLargeInsertion = false;
   mutable std::vector<std::unique_ptr<ReadsTeardown>> _teardowns;  ///< background frees of the current batch call
 };
 

@@ -452,6 +452,147 @@ inline bool isLargeInsertAlignment(const AlignmentScores<int>& scores, const ALI
   return false;
 }
 
+/// blt_util/align_path.cpp:295-329
+inline void apath_limit_read_length(const unsigned target_read_start, const unsigned target_read_end, ALIGNPATH::path_t& apath)
+{
+  bool           isStartSet  = false;
+  unsigned       read_length = 0;
+  const unsigned as          = unsigned(apath.size());
+  unsigned       startSegment = 0, endSegment = as;
+  for (unsigned i = 0; i < as; ++i) {
+    ALIGNPATH::path_segment& ps(apath[i]);
+    if (!ALIGNPATH::is_segment_type_read_length(ps.type)) continue;
+    read_length += ps.length;
+    if (!isStartSet && read_length > target_read_start) {
+      ps.length -= ps.length - (read_length - target_read_start);
+      startSegment = i;
+      isStartSet   = true;
+    }
+    if (read_length >= target_read_end) {
+      if (read_length > target_read_end) ps.length -= (read_length - target_read_end);
+      endSegment = i + 1;
+      break;
+    }
+  }
+  apath = ALIGNPATH::path_t(apath.begin() + startSegment, apath.begin() + endSegment);
+}
+
+/// the per-contig edge test of getSmallSVAssembly (:2079-2113): isLargeInsertAlignment on the path limited to the contig's
+/// conservative range, confirmed on the full path -- a candidate is dropped when the two disagree on left/right; flags and score are
+/// the conservative path's, the offsets the full path's.  `info` is written only for a candidate.
+inline bool isLargeInsertionEdge(
+    const AlignmentScores<int>& scores, const ALIGNPATH::path_t& apath, const pos_t conservativeBegin, const pos_t conservativeEnd,
+    LargeInsertionInfo& info)
+{
+  LargeInsertionInfo insertInfo;
+  ALIGNPATH::path_t  apath_conservative(apath);
+  apath_limit_read_length(unsigned(std::max(conservativeBegin, 0)), unsigned(std::max(conservativeEnd, 0)), apath_conservative);
+  bool isCandidate = isLargeInsertAlignment(scores, apath_conservative, insertInfo);
+  if (isCandidate) {
+    LargeInsertionInfo insertInfo2;
+    isCandidate = isLargeInsertAlignment(scores, apath, insertInfo2);
+    if (insertInfo.isLeftCandidate != insertInfo2.isLeftCandidate || insertInfo.isRightCandidate != insertInfo2.isRightCandidate)
+      isCandidate = false;
+    insertInfo.contigOffset = insertInfo2.contigOffset;
+    insertInfo.refOffset    = insertInfo2.refOffset;
+  }
+  if (isCandidate) info = insertInfo;
+  return isCandidate;
+}
+
+/// processLargeInsertion's choice of the left/right pair (:850-915)
+struct LargeInsertionPair {
+  bool     isPair = false;
+  unsigned leftIndex = 0, rightIndex = 0;  ///< contig indices
+  int      breakDist = 0, breakScore = 0;
+};
+/// candIndex: largeInsertionCandidateIndex; beginPos[i] / info[i]: smallSVAlignments[i].align.beginPos / largeInsertInfo[i] of contig i.
+/// The first pair is accepted unconditionally and replaced only on a strict improvement in (distance, then score).
+inline LargeInsertionPair findLargeInsertionPair(
+    const std::vector<unsigned>& candIndex, const std::vector<pos_t>& beginPos, const std::vector<LargeInsertionInfo>& info)
+{
+  LargeInsertionPair pair;
+  static const int   maxBreakDist(35);
+  const unsigned     candCount = unsigned(candIndex.size());
+  for (unsigned c1 = 0; (c1 + 1) < candCount; ++c1) {
+    const unsigned            i1 = candIndex[c1];
+    const LargeInsertionInfo& insert1(info[i1]);
+    for (unsigned c2 = c1 + 1; c2 < candCount; ++c2) {
+      const unsigned            i2 = candIndex[c2];
+      const LargeInsertionInfo& insert2(info[i2]);
+      if (!((insert1.isLeftCandidate && insert2.isRightCandidate) || (insert2.isLeftCandidate && insert1.isRightCandidate))) continue;
+      const int breakDist = int(std::labs(long(beginPos[i1] + pos_t(insert1.refOffset)) - long(beginPos[i2] + pos_t(insert2.refOffset))));
+      if (breakDist > maxBreakDist) continue;
+      const int  breakScore = insert1.score + insert2.score;
+      const bool isBetter   = (breakDist < pair.breakDist) || ((breakDist == pair.breakDist) && (breakScore > pair.breakScore));
+      if (!pair.isPair || isBetter) {
+        pair.isPair     = true;
+        pair.leftIndex  = i1;
+        pair.rightIndex = i2;
+        if (insert1.isRightCandidate) std::swap(pair.leftIndex, pair.rightIndex);
+        pair.breakDist  = breakDist;
+        pair.breakScore = breakScore;
+      }
+    }
+  }
+  return pair;
+}
+
+/// read-coordinate span of an indel run (:802-830)
+inline known_pos_range2 getInsertTrim(const ALIGNPATH::path_t& apath, const segment_t& segRange)
+{
+  known_pos_range2 range;
+  pos_t            readPos = 0;
+  for (unsigned i = 0; i < apath.size(); ++i) {
+    if (i == segRange.first) range.set_begin_pos(readPos);
+    if (ALIGNPATH::is_segment_type_read_length(apath[i].type)) readPos += pos_t(apath[i].length);
+    if (i == segRange.second) {
+      range.set_end_pos(readPos);
+      return range;
+    }
+  }
+  return range;
+}
+
+/// :642-665
+inline bool isFinishedLargeInsertAlignment(
+    const AlignmentScores<int>& scores, const ALIGNPATH::path_t& apath, const segment_t& insertSegment, const unsigned middleSize)
+{
+  const ALIGNPATH::path_t left(apath.begin(), apath.begin() + insertSegment.second + 1);
+  LargeInsertionInfo      info;
+  info.isLeftCandidate = isLargeInsertSegment(scores, left, info.contigOffset, info.refOffset, info.score, middleSize);
+  ALIGNPATH::path_t rev(apath.begin() + insertSegment.first, apath.end());
+  std::reverse(rev.begin(), rev.end());
+  info.isRightCandidate = isLargeInsertSegment(scores, rev, info.contigOffset, info.refOffset, info.score, middleSize);
+  return info.isLeftCandidate && info.isRightCandidate;
+}
+
+/// processLargeInsertion between the fake contig's alignment (beginPos already moved by the leading cut) and setSmallCandSV (:942-974):
+/// each stage is reached only if the one before it passed, and what a stage did not reach stays cleared
+struct LargeInsertionFinish {
+  std::vector<segment_t> segments;  ///< getLargestInsertSegment(path, middleSize)
+  bool                   isFinished = false;
+  known_pos_range2       insertTrim;  ///< set if isFinished
+  bool                   isFlankOK = false;  ///< both minFlankSize tests pass: the caller goes on to setSmallCandSV
+};
+inline LargeInsertionFinish finishLargeInsertAlignment(
+    const AlignmentScores<int>& completeScores, const ALIGNPATH::path_t& apath, const unsigned leftSize, const unsigned middleSize = 100)
+{
+  LargeInsertionFinish f;
+  f.insertTrim.set_range(0, 0);
+  getLargestInsertSegment(apath, middleSize, f.segments);
+  if (f.segments.size() != 1 || f.segments[0].second < f.segments[0].first) return f;
+  if (!isFinishedLargeInsertAlignment(completeScores, apath, f.segments[0], middleSize)) return f;
+  f.isFinished = true;
+  f.insertTrim = getInsertTrim(apath, f.segments[0]);
+  static const int minFlankSize(40);  // minSemiLargeInsertionLength, SVCandidateAssemblyRefiner.cpp:558
+  if ((f.insertTrim.begin_pos() + minFlankSize) > pos_t(leftSize)) return f;
+  const pos_t rightOffset = pos_t(leftSize + middleSize);
+  if ((rightOffset + minFlankSize) > f.insertTrim.end_pos()) return f;
+  f.isFlankOK = true;
+  return f;
+}
+
 /// :1254-1271
 inline bool isJumpAlignmentQCFail(const JumpAlignmentResult<int>& ja)
 {

@@ -411,6 +411,59 @@ int  manta_spanning_download(manta_spanning_t* b, manta_asm_locus_result_t* loci
                              uint64_t* cigar_arena_used);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Spanning jump-alignment QC and contig selection: what getJumpAssembly derives from the contigs' jump alignments to decide which
+ * contig of a locus is used, and whether it is usable
+ *   isJumpAlignmentQCFail            SVCandidateAssemblyRefiner.cpp:1254-1271 (a path is empty, or its reference length is below 20)
+ *   isLowQualityJumpAlignment        :1287-1309, three QC spans on both sub-alignments, each isLowQualitySpanningSVAlignment (:93-163)
+ *   selectJumpContigDNA              :1364-1398  (is_rna == 0: spans {75, 100, 200}, minimum clipped read length 30; only the first
+ *                                    contig with the strictly highest score among those that pass the QC is tested)
+ *   selectJumpContigRNA              :1312-1358  (is_rna != 0: spans {36, 75, 100} lengthened by the path's spliced length, minimum 20;
+ *                                    every passing contig is tested, then the score / support-read rule over the good ones)
+ * Only the paths, the scores and (RNA) the support bitsets are read: no contig text and no reference text.
+ * Limits: at most 64 contigs per locus, else MANTA_E_UNSUPPORTED in the locus' record and in its contigs' records (never a guess).
+ * A contig whose alignment status is not MANTA_OK carries that status, and so does its locus, which is left undecided.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t  status;       /* MANTA_OK or MANTA_E_* for this contig; a failed alignment's status is carried over */
+  uint32_t qc_fail;      /* isJumpAlignmentQCFail */
+  uint32_t ref_length1, ref_length2;   /* apath_ref_length of align1 / align2 */
+  uint32_t read_length1, read_length2; /* apath_read_length */
+  uint32_t is_tested;    /* isLowQualityJumpAlignment ran on this contig; the three fields below are 0 when it did not */
+  uint32_t span_low;     /* bit s (0..2): align1 is low at span s; bit 3 + s: align2 is low at span s */
+  uint32_t low1, low2;   /* isLowQualityAlign1 / isLowQualityAlign2: low at all three spans */
+} manta_spanning_select_contig_t;
+
+typedef struct {
+  int32_t  status;      /* MANTA_OK or MANTA_E_* for this locus; the fields below are 0 / -1 unless MANTA_OK */
+  uint32_t selected;    /* the static's return value */
+  int32_t  best_contig; /* bestAlignmentIndex: a contig of the locus, 0-based; -1 unless selected */
+  uint32_t n_qc_pass;   /* contigs that pass isJumpAlignmentQCFail */
+  int32_t  max_score;   /* RNA mode: maxAlnScore (:1336-1343); 0 in DNA mode */
+  uint32_t reserved;
+} manta_spanning_select_t;
+
+/* The data arguments are exactly what manta_spanning_download / manta_spanning_batch* return (loci, contigs, alignments, cigar_arena
+ * with *cigar_arena_used as cigar_arena_words, bits_arena with *bits_arena_used as bits_arena_words), handed straight back.
+ * filter_scores: SVRefinerOptions::contigFilterScores (match, mismatch, open, extend are read; match must be positive).
+ * bits_arena may be NULL unless is_rna.  contig_out[i] belongs to contigs[i] (records of contigs no locus refers to are zeroed),
+ * locus_out[l] to loci[l].  A path or bitset that leaves its arena gives its contig MANTA_E_INVALID_ARG; nothing outside is read.
+ * Per-item failures do not stop the batch: the call returns such an item's code and every other record is valid.  A failure of the
+ * call itself (bad arguments, device error) writes no record at all.  The same holds for manta_spanning_download_select. */
+int manta_spanning_select_batch(
+    manta_ctx_t* ctx, const manta_align_scores_t* filter_scores, int32_t is_rna, uint32_t n_loci, const manta_asm_locus_result_t* loci,
+    const manta_asm_contig_t* contigs, const manta_spanning_alignment_t* alignments, const uint32_t* cigar_arena,
+    uint64_t cigar_arena_words, const uint64_t* bits_arena /* may be NULL when !is_rna */, uint64_t bits_arena_words,
+    manta_spanning_select_contig_t* contig_out, manta_spanning_select_t* locus_out);
+
+/* Staged pipeline, opt-in, DNA only: with the stage set, manta_spanning_run launches the selection behind the last aligner pass on
+ * data that never left the device; manta_spanning_download_select returns records index-aligned with the contigs[] and loci[] of
+ * manta_spanning_download (contig_cap / locus_cap: records the caller's arrays hold).  filter_scores == NULL switches the stage off
+ * again.  Without the call nothing about run / stats / output_sizes / download changes. */
+int manta_spanning_set_select(manta_spanning_t* b, const manta_align_scores_t* filter_scores /* NULL = off */);
+int manta_spanning_download_select(manta_spanning_t* b, manta_spanning_select_contig_t* contig_out, uint64_t contig_cap,
+                                   manta_spanning_select_t* locus_out, uint64_t locus_cap);
+
+/* ------------------------------------------------------------------------------------------------------
  * Split-read scoring.  Replaces
  *   void splitReadAligner(flankScoreSize, querySeq, qualConvert, queryQual, targetSeq, targetBpOffsetRange, alignment)
  *                               applications/GenerateSVCandidates/SplitReadAlignment.hpp:57-64 (.cpp:223-350)
@@ -525,7 +578,7 @@ typedef struct {
    an older header would be written past its end.  Check both once after loading the library:
      manta_abi_version() == MANTA_ABI_VERSION  and  manta_batch_stats_size() == sizeof(manta_batch_stats_t)
    (manta_amd/_capi.py does).  The version changes whenever a struct of this header changes size or meaning. */
-#define MANTA_ABI_VERSION 6
+#define MANTA_ABI_VERSION 7
 uint32_t manta_abi_version(void);
 uint64_t manta_batch_stats_size(void);
 

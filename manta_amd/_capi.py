@@ -16,7 +16,7 @@ CIGAR_OPS = "MIDNSHP=X"
 ALIGNER_GLOBAL, ALIGNER_LARGE_INDEL, ALIGNER_JUMP = 0, 1, 2
 
 
-ABI_VERSION = 6  # include/manta_amd.h: MANTA_ABI_VERSION
+ABI_VERSION = 7  # include/manta_amd.h: MANTA_ABI_VERSION
 
 
 class MantaError(RuntimeError):
@@ -837,6 +837,86 @@ class SpanningAlignment(ctypes.Structure):
     _fields_ = [("is_uncut", ctypes.c_int32), ("reserved", ctypes.c_int32), ("align", AlignResult)]
 
 
+class SpanningSelectContig(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32)] + [(n, ctypes.c_uint32) for n in ("qc_fail", "ref_length1", "ref_length2", "read_length1",
+                                                                            "read_length2", "is_tested", "span_low", "low1", "low2")]
+
+
+class SpanningSelect(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("selected", ctypes.c_uint32), ("best_contig", ctypes.c_int32), ("n_qc_pass", ctypes.c_uint32),
+                ("max_score", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+def _decode_select(cs, n_contigs, ls, n_loci):
+    """manta_spanning_select_contig_t / manta_spanning_select_t records -> (one dict per contig, one dict per locus)"""
+    return ([{k: int(getattr(cs[i], k)) for k, _ in SpanningSelectContig._fields_} for i in range(n_contigs)],
+            [{k: int(getattr(ls[l], k)) for k, _ in SpanningSelect._fields_ if k != "reserved"} for l in range(n_loci)])
+
+
+def _select_check(lib, rc, cs, n_contigs, ls, n_loci, strict):
+    """per-item codes are in the records; a code no record carries is the call's own failure"""
+    carried = {cs[i].status for i in range(n_contigs)} | {ls[l].status for l in range(n_loci)}
+    lib._check(rc, allow=() if strict else tuple(c for c in carried if c != 0))
+
+
+def _spanning_select_raw(self, filter_scores, is_rna, loci, contigs, aligns, cig, bits, strict=False, contig_out=None, locus_out=None):
+    """manta_spanning_select_batch on records / arenas laid out as manta_spanning_download returns them (ctypes arrays, numpy arenas cut
+    to what was used; bits None: a NULL bitset arena) -> (one dict per contig record, one dict per locus).  contig_out / locus_out: the
+    caller's own record arrays (to see what a failed call wrote)"""
+    n_loci = len(loci)
+    n = 0
+    for r in loci:
+        if r.status == 0 and r.n_contigs:
+            n = max(n, r.first_contig + r.n_contigs)
+    cs = contig_out if contig_out is not None else (SpanningSelectContig * max(n, 1))()
+    ls = locus_out if locus_out is not None else (SpanningSelect * max(n_loci, 1))()
+    sc = AlignScores(*filter_scores)
+    f = self.lib.manta_spanning_select_batch
+    f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32] + [ctypes.c_void_p] * 4 + [
+        ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+    rc = f(self.ctx, ctypes.byref(sc), int(is_rna), n_loci, loci, contigs, aligns, _p(cig), ctypes.c_uint64(len(cig)),
+           _p(bits) if bits is not None else None, ctypes.c_uint64(len(bits) if bits is not None else 0), cs, ls)
+    _select_check(self, rc, cs, n, ls, n_loci, strict)
+    return _decode_select(cs, n, ls, n_loci)
+
+
+def _spanning_select_batch(self, filter_scores, is_rna, loci_items, strict=False):
+    """loci_items: per locus a list of contigs, each a dict of `cigar1`, `cigar2` (text), `score` and optionally `status` (of its
+    alignment) and `support` (read indices; RNA mode) -> (per locus a list of contig dicts, one dict per locus)"""
+    n_loci = len(loci_items)
+    n = sum(len(it) for it in loci_items)
+    loci, contigs, aligns = (AsmLocusResult * max(n_loci, 1))(), (AsmContig * max(n, 1))(), (SpanningAlignment * max(n, 1))()
+    cig, bits = [], []
+    i = 0
+    for l, items in enumerate(loci_items):
+        n_words = max([1] + [(max(c.get("support", [0]) or [0]) + 64) // 64 for c in items])
+        loci[l].n_contigs, loci[l].first_contig, loci[l].n_words = len(items), i, n_words
+        for c in items:
+            w1, w2 = pack_cigar(c["cigar1"]), pack_cigar(c["cigar2"])
+            a = aligns[i].align
+            a.status, a.score = c.get("status", 0), c["score"]
+            a.cigar1_off, a.cigar1_len = len(cig), len(w1)
+            a.cigar2_off, a.cigar2_len = len(cig) + len(w1), len(w2)
+            cig += w1 + w2
+            words = [0] * (2 * n_words)
+            for r in c.get("support", []):
+                words[r // 64] |= 1 << (r % 64)
+            contigs[i].support_off, contigs[i].reject_off = len(bits), len(bits) + n_words
+            bits += words
+            i += 1
+    cs, ls = _spanning_select_raw(self, filter_scores, is_rna, loci, contigs, aligns, np.array(cig, dtype=np.uint32),
+                                  np.array(bits, dtype=np.uint64), strict=strict)
+    per_locus, i = [], 0
+    for it in loci_items:
+        per_locus.append(cs[i:i + len(it)])
+        i += len(it)
+    return per_locus, ls[:n_loci]
+
+
+Lib.spanning_select_raw = _spanning_select_raw
+Lib.spanning_select_batch = _spanning_select_batch
+
+
 class SpanningBatch:
     """Staged fused spanning pipeline (manta_spanning_*): assemble -> jump-align on cut references -> re-align rule."""
 
@@ -906,7 +986,28 @@ class SpanningBatch:
             ctypes.byref(su), bits.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(bits_cap), ctypes.byref(bu),
             cig.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(cig_cap), ctypes.byref(cu))
         self.lib._check(rc, allow=() if strict else (-4, -5, -6, -7))
+        # the records and arenas as downloaded, cut to what was used (manta_spanning_select_batch takes them as they are)
+        self.raw = (res, contigs, aligns, seq[:int(su.value)], bits[:int(bu.value)], cig[:int(cu.value)])
         return _decode_loci("spanning", self.n_reads, res, contigs, aligns, seq, bits, cig)
+
+    def set_select(self, filter_scores):
+        """jump-alignment QC and contig selection (DNA) behind the last aligner pass of every later run (filter_scores None: off again)"""
+        f = self.lib.lib.manta_spanning_set_select
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        sc = AlignScores(*filter_scores) if filter_scores is not None else None
+        self.lib._check(f(self.h, ctypes.byref(sc) if sc is not None else None))
+
+    def download_select(self, strict=False):
+        """records of the last run, index-aligned with the contig and locus records of download() -> (one dict per contig, one per locus)"""
+        sizes = [ctypes.c_uint64(0) for _ in range(4)]
+        self.lib._check(self.lib.lib.manta_spanning_output_sizes(self.h, *[ctypes.byref(x) for x in sizes]))
+        cap, n_loci = max(1, int(sizes[0].value)), self.n_loci
+        cs, ls = (SpanningSelectContig * cap)(), (SpanningSelect * max(n_loci, 1))()
+        f = self.lib.lib.manta_spanning_download_select
+        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]
+        rc = f(self.h, cs, ctypes.c_uint64(cap), ls, ctypes.c_uint64(max(n_loci, 1)))
+        _select_check(self.lib, rc, cs, cap, ls, n_loci, strict)
+        return _decode_select(cs, cap, ls, n_loci)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -1345,6 +1345,11 @@ int spanningRunImpl(manta_spanning_t* b, StageGates* gates)
     b->evAlign.record();
     finishRun(b, earlyStage, alignOnly);
     stage("aligned round 2");
+    b->selRan = false;
+    if (b->selOn) {  // jump-alignment QC and contig selection on the paths where they are (manta_spanning_set_select); outside the timed stages
+      spanningSelLaunch(b);
+      stage("select");
+    }
     b->ran = true;
     return MANTA_OK;
   } catch (const std::exception& e) {

@@ -31,6 +31,7 @@
 #include "read_class_kernels.hpp"
 #include "smallsv_qc_kernels.hpp"
 #include "smallsv_li_kernels.hpp"
+#include "spanning_select_kernels.hpp"
 #include <unordered_map>
 #include "rt.hpp"
 #include "host_pool.hpp"
@@ -121,6 +122,8 @@ struct manta_ctx {
   DevBuf dRc[16];  // manta_read_piles_batch: inputs, workspace, outputs
   DevBuf dQc[6];   // manta_smallsv_qc_batch / manta_seq_match_count_batch: tasks, records, segments, counters, references, texts
   DevBuf dLi[14];  // manta_smallsv_large_insertion_batch: inputs (tasks, loci, texts, paths, references) and the stage's buffers (LiBufs)
+  DevBuf dSel[7];  // manta_spanning_select_batch: tasks, loci, paths, bitsets, contig records, locus records, queue head
+  rt::Event evSel[2];  // around spanning_select_kernel (selLaunch; read under MANTA_AMD_DEBUG)
   rt::Stream stream;  // the context's own stream (manta_align_batch / manta_assemble_batch run on it)
   int        deviceId = 0;
   // worker pipelines of the whole-batch calls (manta_smallsv_batch / manta_spanning_batch), kept across calls
@@ -1690,6 +1693,10 @@ struct manta_spanning : PipeBase {
   DevBuf                dPassMask;
   uint32_t              earlyLoci = 0;      // loci the last run aligned early
   std::vector<JumpCuts> hostCuts;  // the caller's cuts of the uploaded batch
+  // jump-alignment QC and contig selection behind the last aligner pass (manta_spanning_set_select; off unless asked for)
+  bool                  selOn = false, selRan = false;
+  manta_align_scores_t  selScores{};
+  DevBuf                dSelContigs, dSelLoci, dSelCnt;
   using PipeBase::PipeBase;
 };
 
@@ -1743,10 +1750,7 @@ inline void launchPack(PipeBase* b, const AlignTaskDev* tasks, const AlignTaskDe
 
 inline void qcSetScores(QcParams& Q, const manta_align_scores_t& sc, uint32_t minIndel)
 {
-  Q.match     = sc.match;
-  Q.mismatch  = sc.mismatch;
-  Q.open      = sc.open;
-  Q.extend    = sc.extend;
+  Q.sc        = QcScores{sc.match, sc.mismatch, sc.open, sc.extend};
   Q.min_indel = minIndel;
 }
 inline int qcGrid(const manta_ctx_t* ctx, uint64_t units)
@@ -2048,6 +2052,101 @@ inline void smallsvLiLaunch(manta_smallsv* b)
   liLaunch(b->ctx, L, uint64_t(b->nLoci) * b->opt.max_assembly_count, b->asmStage.maxContigLen, b->liCompleteScores, b->dLi);
   b->liParams = L;
   b->liRan    = true;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// spanning jump-alignment QC and contig selection (spanning_select_kernels.hpp)
+// ------------------------------------------------------------------------------------------------------
+/// the kernel on the inputs `S` names (the stand-alone call's staged records or a pipeline's own state); the caller holds the stream.
+/// nContigRecs: records of S.contig_out, zeroed here (a contig no locus refers to keeps a zeroed record).
+inline void selLaunch(manta_ctx_t* ctx, SelParams& S, const uint64_t nContigRecs, DevBuf& contigBuf, DevBuf& locusBuf, DevBuf& cntBuf)
+{
+  S.contig_out = contigBuf.as<SelContigDev>(nContigRecs + 1);
+  S.locus_out  = locusBuf.as<SelLocusRecDev>(uint64_t(S.n_units) + 1);
+  S.counter    = cntBuf.as<uint32_t>(4);
+  rt::dzero(S.contig_out, sizeof(SelContigDev) * (nContigRecs + 1));
+  rt::dzero(S.counter, 16);
+  ctx->evSel[0].record();
+  rt::launch(spanning_select_kernel, qcGrid(ctx, S.n_units), 0, S);
+  ctx->evSel[1].record();
+}
+/// MANTA_AMD_DEBUG: the kernel's own time from its HIP events (the caller has waited for the stream)
+inline void selReport(manta_ctx_t* ctx, const SelParams& S, const char* who)
+{
+  if (!std::getenv("MANTA_AMD_DEBUG")) return;
+  std::fprintf(stderr, "manta_amd: %s: spanning_select_kernel %.3f ms for %u loci (HIP events)\n", who, rt::elapsedMs(ctx->evSel[0], ctx->evSel[1]), S.n_units);
+}
+
+/// device records -> the caller's records.  contigOf(i): index of output contig i's device record, or -1 (zeroed); locusStatus(l):
+/// MANTA_OK, or the code of a locus the kernel did not look at.  Nothing can fail here: a failure of the call as a whole is found
+/// before this is reached.
+template <typename ContigOf, typename LocusStatus>
+int selCompact(manta_ctx_t* ctx, const std::vector<SelContigDev>& hContigs, const std::vector<SelLocusRecDev>& hLoci, uint64_t nContigsOut,
+               ContigOf contigOf, LocusStatus locusStatus, manta_spanning_select_contig_t* contig_out, manta_spanning_select_t* locus_out, const char* who)
+{
+  int worst = MANTA_OK;
+  for (uint64_t i = 0; i < nContigsOut; ++i) {
+    manta_spanning_select_contig_t& o(contig_out[i]);
+    std::memset(&o, 0, sizeof(o));
+    const int64_t at = contigOf(i);
+    if (at < 0) continue;
+    const SelContigDev& d(hContigs[size_t(at)]);
+    o.status = d.status;
+    if (o.status != MANTA_OK) {
+      worst = o.status;
+      continue;
+    }
+    o.qc_fail      = d.qc_fail;
+    o.ref_length1  = d.ref_length1;
+    o.ref_length2  = d.ref_length2;
+    o.read_length1 = d.read_length1;
+    o.read_length2 = d.read_length2;
+    o.is_tested    = d.tested;
+    o.span_low     = d.span_low;
+    o.low1         = d.low1;
+    o.low2         = d.low2;
+  }
+  for (uint64_t l = 0; l < hLoci.size(); ++l) {
+    manta_spanning_select_t& o(locus_out[l]);
+    std::memset(&o, 0, sizeof(o));
+    const SelLocusRecDev& d(hLoci[l]);
+    o.status      = (locusStatus(l) != MANTA_OK) ? locusStatus(l) : d.status;
+    o.best_contig = -1;
+    if (o.status != MANTA_OK) {
+      worst = o.status;
+      continue;
+    }
+    o.selected    = d.selected;
+    o.best_contig = d.best_contig;
+    o.n_qc_pass   = d.n_qc_pass;
+    o.max_score   = d.max_score;
+  }
+  if (worst != MANTA_OK) return fail(ctx, worst, std::string(who) + ": one or more items failed; see per-item status");
+  return MANTA_OK;
+}
+
+/// the selection on a finished run's own device state (manta_spanning_set_select); the caller holds the pipeline's stream and has waited
+/// for the last aligner pass
+inline void spanningSelLaunch(manta_spanning* b)
+{
+  const uint64_t nSlots = uint64_t(b->nLoci) * b->opt.max_assembly_count;
+  SelParams      S;
+  std::memset(&S, 0, sizeof(S));
+  S.n_units            = b->nLoci;
+  S.is_rna             = 0;
+  S.loci               = b->asmStage.dLoci;
+  S.max_assembly_count = b->opt.max_assembly_count;
+  S.atasks             = static_cast<const AlignTaskDev*>(b->dTasks.p);
+  S.atasks2            = static_cast<const AlignTaskDev*>(b->dTasks2.p);
+  S.results            = static_cast<const AlignResultDev*>(b->dResults.p);
+  S.results2           = static_cast<const AlignResultDev*>(b->dResults2.p);
+  S.info               = static_cast<const SpanTaskInfo*>(b->dInfo.p);
+  S.cigar              = static_cast<const uint32_t*>(b->dCigar.p);
+  S.sc                 = QcScores{b->selScores.match, b->selScores.mismatch, b->selScores.open, b->selScores.extend};
+  selLaunch(b->ctx, S, nSlots, b->dSelContigs, b->dSelLoci, b->dSelCnt);
+  rt::sync();
+  selReport(b->ctx, S, "manta_spanning_run");
+  b->selRan = true;
 }
 
 inline int checkPiles(manta_ctx_t* ctx, const manta_packed_piles_t* pl, const char* who)

@@ -521,6 +521,150 @@ extern "C" int manta_smallsv_download_large_insertion(manta_smallsv_t* b, manta_
   }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// spanning jump-alignment QC and contig selection (spanning_select_kernels.hpp)
+// ------------------------------------------------------------------------------------------------------
+extern "C" int manta_spanning_select_batch(
+    manta_ctx_t* ctx, const manta_align_scores_t* filter_scores, int32_t is_rna, uint32_t n_loci, const manta_asm_locus_result_t* loci,
+    const manta_asm_contig_t* contigs, const manta_spanning_alignment_t* alignments, const uint32_t* cigar_arena, uint64_t cigar_arena_words,
+    const uint64_t* bits_arena, uint64_t bits_arena_words, manta_spanning_select_contig_t* contig_out, manta_spanning_select_t* locus_out)
+{
+  static const char* fn = "manta_spanning_select_batch";
+  if (!ctx) return MANTA_E_INVALID_ARG;
+  if (!filter_scores || (n_loci && (!loci || !locus_out))) return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": null argument");
+  // (the reference asserts optimalScore > 0: the score fraction divides by clipped length x match)
+  if (filter_scores->match <= 0) return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": filter_scores->match must be positive");
+  if (is_rna && !bits_arena) return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": bits_arena is null in RNA mode");
+  if (n_loci == 0) return MANTA_OK;
+  uint64_t nContigs = 0;
+  for (uint32_t l = 0; l < n_loci; ++l) {
+    if (loci[l].status != MANTA_OK || loci[l].n_contigs == 0) continue;
+    nContigs = std::max<uint64_t>(nContigs, uint64_t(loci[l].first_contig) + loci[l].n_contigs);
+  }
+  if (nContigs && (!contigs || !alignments || !contig_out || (cigar_arena_words && !cigar_arena)))
+    return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": null argument");
+  std::vector<uint8_t> seen(nContigs + 1, 0);
+  for (uint32_t l = 0; l < n_loci; ++l) {
+    if (loci[l].status != MANTA_OK) continue;
+    for (uint32_t c = 0; c < loci[l].n_contigs; ++c) {
+      const uint64_t i = uint64_t(loci[l].first_contig) + c;
+      if (seen[i]) return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": contig record " + std::to_string(i) + " belongs to two loci");
+      seen[i] = 1;
+    }
+  }
+  try {
+    rt::setDevice(ctx->deviceId);
+    rt::ScopedStream onStream(ctx->stream);
+    DevBuf* const   B     = ctx->dSel;
+    const uint64_t  nBits = is_rna ? bits_arena_words : 0;
+    const uint32_t* dCig  = B[2].as<uint32_t>(cigar_arena_words + 4);
+    const uint64_t* dBits = B[3].as<uint64_t>(nBits + 2);
+    std::vector<SelTaskDev>  hTasks(nContigs + 1);
+    std::vector<SelLocusDev> hLoci(n_loci);
+    auto outside = [](uint64_t off, uint64_t len, uint64_t size) { return off > size || len > size - off; };
+    for (uint32_t l = 0; l < n_loci; ++l) {
+      SelLocusDev& u(hLoci[l]);
+      u.first    = loci[l].first_contig;
+      u.n        = (loci[l].status == MANTA_OK) ? loci[l].n_contigs : 0u;
+      u.status   = loci[l].status;
+      u.reserved = 0;
+      for (uint32_t c = 0; c < u.n; ++c) {
+        const uint64_t              i = uint64_t(u.first) + c;
+        const manta_align_result_t& a(alignments[i].align);
+        SelTaskDev&                 t(hTasks[i]);
+        std::memset(&t, 0, sizeof(t));
+        t.status = a.status;
+        t.score  = a.score;
+        t.cigar1 = t.cigar2 = dCig;
+        t.support           = is_rna ? dBits : nullptr;
+        if (a.status != MANTA_OK) continue;
+        // nothing outside the caller's arenas is ever read
+        if (outside(a.cigar1_off, a.cigar1_len, cigar_arena_words) || outside(a.cigar2_off, a.cigar2_len, cigar_arena_words) ||
+            (is_rna && outside(contigs[i].support_off, loci[l].n_words, nBits))) {
+          t.status = MANTA_E_INVALID_ARG;
+          continue;
+        }
+        t.cigar1   = dCig + a.cigar1_off;
+        t.n_cigar1 = a.cigar1_len;
+        t.cigar2   = dCig + a.cigar2_off;
+        t.n_cigar2 = a.cigar2_len;
+        if (is_rna) {
+          t.support = dBits + contigs[i].support_off;
+          t.n_words = loci[l].n_words;
+        }
+      }
+    }
+    SelParams S;
+    std::memset(&S, 0, sizeof(S));
+    SelTaskDev*  dTasks = B[0].as<SelTaskDev>(nContigs + 1);
+    SelLocusDev* dLoci  = B[1].as<SelLocusDev>(n_loci);
+    S.tasks   = dTasks;
+    S.units   = dLoci;
+    S.n_units = n_loci;
+    S.is_rna  = is_rna ? 1u : 0u;
+    S.sc      = QcScores{filter_scores->match, filter_scores->mismatch, filter_scores->open, filter_scores->extend};
+    if (cigar_arena_words) rt::h2d(const_cast<uint32_t*>(dCig), cigar_arena, 4 * cigar_arena_words);
+    if (nBits) rt::h2d(const_cast<uint64_t*>(dBits), bits_arena, 8 * nBits);
+    rt::h2d(dTasks, hTasks.data(), sizeof(SelTaskDev) * (nContigs + 1));
+    rt::h2d(dLoci, hLoci.data(), sizeof(SelLocusDev) * n_loci);
+    selLaunch(ctx, S, nContigs, B[4], B[5], B[6]);
+    std::vector<SelContigDev>   hC(nContigs + 1);
+    std::vector<SelLocusRecDev> hL(n_loci);
+    rt::d2hAsync(hC.data(), S.contig_out, sizeof(SelContigDev) * (nContigs + 1));
+    rt::d2hAsync(hL.data(), S.locus_out, sizeof(SelLocusRecDev) * n_loci);
+    rt::sync();
+    selReport(ctx, S, fn);
+    return selCompact(ctx, hC, hL, nContigs, [&](uint64_t i) { return seen[i] ? int64_t(i) : int64_t(-1); }, [&](uint64_t) { return int(MANTA_OK); },
+                      contig_out, locus_out, fn);
+  } catch (const std::exception& e) {
+    return fail(ctx, MANTA_E_HIP, e.what());
+  }
+}
+
+extern "C" int manta_spanning_set_select(manta_spanning_t* b, const manta_align_scores_t* filter_scores)
+{
+  if (!b) return MANTA_E_INVALID_ARG;
+  if (filter_scores && filter_scores->match <= 0) return fail(b->ctx, MANTA_E_INVALID_ARG, "manta_spanning_set_select: filter_scores->match must be positive");
+  b->selOn  = filter_scores != nullptr;
+  b->selRan = false;
+  if (filter_scores) b->selScores = *filter_scores;
+  return MANTA_OK;
+}
+
+extern "C" int manta_spanning_download_select(manta_spanning_t* b, manta_spanning_select_contig_t* contig_out, uint64_t contig_cap,
+                                              manta_spanning_select_t* locus_out, uint64_t locus_cap)
+{
+  static const char* fn = "manta_spanning_download_select";
+  if (!b) return MANTA_E_INVALID_ARG;
+  manta_ctx_t* ctx = b->ctx;
+  if (!b->ran || !b->selOn || !b->selRan)
+    return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": no run with the stage set (manta_spanning_set_select, then manta_spanning_run)");
+  try {
+    rt::setDevice(ctx->deviceId);
+    rt::ScopedStream onStream(b->main);
+    const uint32_t nLoci  = b->nLoci, maxAsm = b->opt.max_assembly_count;
+    const uint64_t nSlots = uint64_t(nLoci) * maxAsm;
+    std::vector<AsmLocusOut>    hLoci(nLoci);
+    std::vector<SelContigDev>   hC(nSlots + 1);
+    std::vector<SelLocusRecDev> hL(nLoci);
+    rt::d2hAsync(hLoci.data(), b->asmStage.dLoci, sizeof(AsmLocusOut) * nLoci);
+    rt::d2hAsync(hC.data(), b->dSelContigs.p, sizeof(SelContigDev) * nSlots);
+    rt::d2hAsync(hL.data(), b->dSelLoci.p, sizeof(SelLocusRecDev) * nLoci);
+    rt::sync();
+    // contigs[] of manta_spanning_download: the loci in order, every locus' contigs in order (AsmStage::compact)
+    std::vector<uint64_t> slotOf;
+    for (uint32_t l = 0; l < nLoci; ++l)
+      if (hLoci[l].status == ASM_OK)
+        for (uint32_t c = 0; c < hLoci[l].n_contigs; ++c) slotOf.push_back(uint64_t(l) * maxAsm + c);
+    if (slotOf.size() > contig_cap || (!slotOf.empty() && !contig_out) || nLoci > locus_cap || (nLoci && !locus_out))
+      return fail(ctx, MANTA_E_CAPACITY, std::string(fn) + ": record array too small");
+    return selCompact(ctx, hC, hL, slotOf.size(), [&](uint64_t i) { return int64_t(slotOf[i]); },
+                      [&](uint64_t l) { return asmStatusToAbi(hLoci[l].status); }, contig_out, locus_out, fn);
+  } catch (const std::exception& e) {
+    return fail(ctx, MANTA_E_HIP, e.what());
+  }
+}
+
 extern "C" int manta_seq_match_count_batch(
     manta_ctx_t* ctx, uint32_t n_tasks, const manta_seq_match_task_t* tasks, const uint8_t* seq_arena, uint64_t seq_bytes, uint32_t* counts)
 {

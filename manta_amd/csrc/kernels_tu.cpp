@@ -25,6 +25,7 @@
 #include "read_class_kernels.hpp"
 #include "smallsv_qc_kernels.hpp"
 #include "smallsv_li_kernels.hpp"
+#include "spanning_select_kernels.hpp"
 #else
 #error "unknown MANTA_TU"
 #endif

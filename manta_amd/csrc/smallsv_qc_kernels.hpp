@@ -36,6 +36,11 @@ static const unsigned QC_SEG_PAIRS     = 3 * QC_MAX_RUNS;      // (first,last) p
 // per-item status: the C ABI's codes (include/manta_amd.h)
 static const int QC_OK = 0, QC_E_INVALID_ARG = -1, QC_E_UNSUPPORTED = -5, QC_E_CAPACITY = -6, QC_E_DEVICE_FAULT = -7;
 
+/// what getPathScore reads of an AlignmentScores: the contig filter scores, SVRefinerOptions::contigFilterScores
+struct QcScores {
+  int32_t match, mismatch, open, extend;
+};
+
 struct QcTaskDev {
   const uint8_t*  contig;
   const uint32_t* cigar;  ///< BAM-packed segments, (len << 4) | op
@@ -69,8 +74,7 @@ struct QcParams {
   const AlignResultDev*  results;
   const SmallSvTaskInfo* info;
   const uint32_t*        cigar;
-  // contig filter scores, SVRefinerOptions::contigFilterScores
-  int32_t  match, mismatch, open, extend;
+  QcScores sc;         ///< contig filter scores
   uint32_t min_indel;  ///< minCandidateIndelSize
   // outputs
   QcRecordDev* out;       ///< per task / per (locus, contig slot)
@@ -124,6 +128,37 @@ WV_DEV uint64_t qcBitRange(const int lo, const int hi)  // bits lo..hi
 {
   const uint64_t upTo = (hi >= 63) ? ~uint64_t(0) : ((uint64_t(1) << (hi + 1)) - 1);
   return upTo & ~((uint64_t(1) << lo) - 1);
+}
+
+/// soft clips at the two ends of a path (hard clips skipped: apath_soft_clip_right_size of the path and of its reverse), fed the path's
+/// segments 64 per round in path order
+struct QcClips {
+  unsigned lead, trail;
+  bool     leading;  ///< no segment other than a clip seen yet
+};
+WV_DEV QcClips qcClips()
+{
+  QcClips C;
+  C.lead = C.trail = 0;
+  C.leading = true;
+  return C;
+}
+WV_DEV void qcClipRound(QcClips& C, const bool valid, const unsigned op, const unsigned len)
+{
+  const int      lane = wv::lane();
+  const unsigned sl   = (valid && op == 4u) ? len : 0u;
+  const uint64_t mNC  = wv::ballot(valid && op != 4u && op != 5u);
+  if (C.leading) {
+    const int f = mNC ? wv::ctz(mNC) : 64;
+    C.lead += qcSum((lane < f) ? sl : 0u);
+    C.leading = (mNC == 0);
+  }
+  if (mNC) {
+    const int lastNC = 63 - wv::clz(mNC);
+    C.trail          = qcSum((lane > lastNC) ? sl : 0u);
+  } else {
+    C.trail += qcSum(sl);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -235,7 +270,8 @@ WV_DEV QcRuns qcFindRuns(const uint32_t* cig, const unsigned n, const unsigned m
   R.first = R.last = R.readBefore = R.readThrough = R.maxIndel = 0;
   R.nRuns = R.totRead = R.totRef = R.leadClip = R.trailClip = 0;
   // a run that reaches the last lane of a step stays open: whether it ends there is known from the next step's first segment
-  bool     open = false, oBig = false, leading = true;
+  bool     open = false, oBig = false;
+  QcClips  clips = qcClips();
   unsigned oFirst = 0, oReadBefore = 0, oMax = 0;
   for (unsigned base = 0; base < n; base += 64) {
     const unsigned i     = base + unsigned(lane);
@@ -247,20 +283,7 @@ WV_DEV QcRuns qcFindRuns(const uint32_t* cig, const unsigned n, const unsigned m
     const bool     indel = valid && (op == 1u || op == 2u);
     const unsigned inclR = qcScanIncl(rl) + R.totRead, inclF = qcScanIncl(fl) + R.totRef;
     const uint64_t mI = wv::ballot(indel), mBig = wv::ballot(indel && len >= minIndel);
-    // soft clips at the two ends
-    const unsigned sl  = (valid && op == 4u) ? len : 0u;
-    const uint64_t mNC = wv::ballot(valid && op != 4u && op != 5u);
-    if (leading) {
-      const int f = mNC ? wv::ctz(mNC) : 64;
-      R.leadClip += qcSum((lane < f) ? sl : 0u);
-      leading = (mNC == 0);
-    }
-    if (mNC) {
-      const int lastNC = 63 - wv::clz(mNC);
-      R.trailClip      = qcSum((lane > lastNC) ? sl : 0u);
-    } else {
-      R.trailClip += qcSum(sl);
-    }
+    qcClipRound(clips, valid, op, len);
     // the open run ended with the previous step
     if (open && !(mI & 1u)) {
       if (oBig) qcRecordRun(R, oFirst, base - 1, oReadBefore, R.totRead, oMax);
@@ -302,32 +325,39 @@ WV_DEV QcRuns qcFindRuns(const uint32_t* cig, const unsigned n, const unsigned m
     R.totRead = wv::shfl(inclR, 63);
     R.totRef  = wv::shfl(inclF, 63);
   }
+  R.leadClip  = clips.lead;
+  R.trailClip = clips.trail;
   return R;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// step 2: isLowQualitySmallSVAlignment (:318-388) on the flank before segment `edge` (leading) or after it (trailing)
+// step 2: the flank walk of isLowQualitySmallSVAlignment (:318-388) and isLowQualitySpanningSVAlignment (:93-163)
 // ------------------------------------------------------------------------------------------------------------------
-WV_DEV int qcSegScore(const QcParams& P, const unsigned op, const unsigned len)  // getPathScore, off-edge not scored (AlignmentScoringUtil.hpp:37)
+WV_DEV int qcSegScore(const QcScores& sc, const unsigned op, const unsigned len)  // getPathScore, off-edge not scored (AlignmentScoringUtil.hpp:37)
 {
-  if (op == 7u) return P.match * int(len);
-  if (op == 8u) return P.mismatch * int(len);
-  if (op == 1u || op == 2u) return P.open + P.extend * int(len);
+  if (op == 7u) return sc.match * int(len);
+  if (op == 8u) return sc.mismatch * int(len);
+  if (op == 1u || op == 2u) return sc.open + sc.extend * int(len);
   return 0;
 }
 
-WV_DEV bool qcFlankLow(const QcParams& P, const uint32_t* cig, const unsigned n, const bool isLeading, const unsigned edge,
-                       const unsigned maxQCRefSpan, const unsigned minSpan, const unsigned clipIfUncut)
+/// The flank is the segments [begin, end) of the path, walked away from the breakend: a leading flank from end - 1 downwards (the
+/// reference reverses it), a trailing one from `begin` upwards.  Its first maxQCRefSpan reference bases are kept (apath_limit_ref_length);
+/// low: fewer than minRefSpan reference bases (the small-SV flavour; 0 for the spanning one, which has no such test), fewer than
+/// minReadLength read bases before the far soft clip, or less than 3/4 of the perfect score.  clipIfUncut: the soft clip at the far end
+/// of the flank, which counts only when the walk was not cut.
+WV_DEV bool qcFlankLow(const QcScores& sc, const uint32_t* cig, const bool isLeading, const unsigned begin, const unsigned end,
+                       const unsigned maxQCRefSpan, const unsigned minRefSpan, const unsigned minReadLength, const unsigned clipIfUncut)
 {
   const int      lane  = wv::lane();
-  const unsigned count = isLeading ? edge : (n - 1 - edge);  // segments of the flank, walked away from the breakend
+  const unsigned count = end - begin;
   unsigned       covered = 0, readSize = 0;
   int            score = 0;
   bool           cut   = false;
   for (unsigned t0 = 0; t0 < count && !cut; t0 += 64) {
     const unsigned t     = t0 + unsigned(lane);
     const bool     valid = t < count;
-    const unsigned j     = isLeading ? (edge - 1 - t) : (edge + 1 + t);
+    const unsigned j     = isLeading ? (end - 1 - t) : (begin + t);
     const uint32_t w     = valid ? cig[j] : 0u;
     const unsigned op = w & 15u, len = w >> 4;
     const bool     isRef = valid && qcIsRefLen(op);
@@ -343,16 +373,16 @@ WV_DEV bool qcFlankLow(const QcParams& P, const uint32_t* cig, const unsigned n,
       cut = true;
     }
     readSize += qcSum((in && qcIsReadLen(op)) ? eff : 0u);
-    score += int(qcSum(unsigned(in ? qcSegScore(P, op, eff) : 0)));
+    score += int(qcSum(unsigned(in ? qcSegScore(sc, op, eff) : 0)));
     covered = wv::shfl(incl, 63);
   }
   const unsigned refSpan = cut ? maxQCRefSpan : covered;
-  if (refSpan < minSpan) return true;
+  if (refSpan < minRefSpan) return true;
   // a cut path ends on a reference-consuming segment: no soft clip at its far end
   const unsigned clippedSize = readSize - (cut ? 0u : clipIfUncut);
-  if (clippedSize < minSpan) return true;
+  if (clippedSize < minReadLength) return true;
   const int   nonClipScore = (score > 0) ? score : 0;
-  const int   optimalScore = int(clippedSize) * P.match;
+  const int   optimalScore = int(clippedSize) * sc.match;
   const float scoreFrac    = float(nonClipScore) / float(optimalScore);
   return scoreFrac < 0.75f;
 }
@@ -393,7 +423,7 @@ WV_DEV QcRecordDev qcTask(const QcParams& P, const QcTaskDev& T, uint8_t* lds)
       // candidates are dropped from the left until the flank before the first one is clean, then from the right (:452-492); a list
       // that would become empty ends the span with its last element, as the reference's vector does
       while (true) {
-        if (!qcFlankLow(P, T.cigar, T.n_cigar, true, wv::shfl(R.first, int(lo)), maxQCRefSpan, minSpan, R.leadClip)) break;
+        if (!qcFlankLow(P.sc, T.cigar, true, 0, wv::shfl(R.first, int(lo)), maxQCRefSpan, minSpan, minSpan, R.leadClip)) break;
         if (lo == hi) {
           cand = false;
           break;
@@ -401,7 +431,7 @@ WV_DEV QcRecordDev qcTask(const QcParams& P, const QcTaskDev& T, uint8_t* lds)
         ++lo;
       }
       while (cand) {
-        if (!qcFlankLow(P, T.cigar, T.n_cigar, false, wv::shfl(R.last, int(hi)), maxQCRefSpan, minSpan, R.trailClip)) break;
+        if (!qcFlankLow(P.sc, T.cigar, false, wv::shfl(R.last, int(hi)) + 1, T.n_cigar, maxQCRefSpan, minSpan, minSpan, R.trailClip)) break;
         if (lo == hi) {
           cand = false;
           break;

@@ -23,7 +23,8 @@
 #define MANTA_TU_ALIGN2 10      // align_kernel<2, E>
 #define MANTA_TU_ALIGN_PAIR 11  // align_pair_kernel<E>, align_pair_multi_kernel
 #define MANTA_TU_JUMP_PAIR 12   // align_jump_pair_kernel<E>
-#define MANTA_TU_GLUE 13        // pipeline_kernels.hpp, split_kernels.hpp, read_class_kernels.hpp, smallsv_qc_kernels.hpp, smallsv_li_kernels.hpp
+#define MANTA_TU_GLUE 13        // pipeline_kernels.hpp, split_kernels.hpp, read_class_kernels.hpp, smallsv_qc_kernels.hpp, smallsv_li_kernels.hpp,
+                                // spanning_select_kernels.hpp
 #define MANTA_TU_ALIGN3 14      // align_kernel<3, E>
 #define MANTA_TU_COUNT 15
 #ifndef MANTA_TU

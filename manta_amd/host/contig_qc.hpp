@@ -45,6 +45,16 @@ inline bool liCallFailed(const int rc, const std::vector<manta_large_insert_edge
     if (l.status == rc) return false;
   return true;
 }
+/// ... and manta_spanning_select_batch / manta_spanning_download_select
+inline bool selectCallFailed(const int rc, const std::vector<manta_spanning_select_contig_t>& contigs, const std::vector<manta_spanning_select_t>& loci)
+{
+  if (rc == MANTA_OK) return false;
+  for (const manta_spanning_select_contig_t& c : contigs)
+    if (c.status == rc) return false;
+  for (const manta_spanning_select_t& l : loci)
+    if (l.status == rc) return false;
+  return true;
+}
 }  // namespace detail
 
 /// one contig alignment of the batch: getSmallSVAssembly's alignment.align, contig.seq and align1RefStr
@@ -274,6 +284,127 @@ inline void findLargeInsertionBatch(
     r.finish.isFinished = d.is_finished != 0;
     r.finish.insertTrim.set_range(d.trim_begin, d.trim_end);
     r.finish.isFlankOK = d.is_flank_ok != 0;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// spanning jump-alignment QC and contig selection (manta_spanning_select_batch) over the adapter types
+// ------------------------------------------------------------------------------------------------------
+/// The device half alone, on a spanning batch's own output handed back as it came (manta_spanning_batch / manta_spanning_download):
+/// contigRecs[i] belongs to contigs[i], locusRecs[l] to loci[l].  A locus whose record carries a status was not decided: the caller
+/// recomputes it with selectJumpContigDNA / selectJumpContigRNA.  cigarWords / bitsWords: what the arenas hold (the records' reach is
+/// what is uploaded); bits may be nullptr unless isRNA.
+inline void selectJumpContigBatch(
+    manta_ctx_t* ctx, const AlignmentScores<int>& contigFilterScores, const bool isRNA, const uint32_t nLoci, const manta_asm_locus_result_t* loci,
+    const manta_asm_contig_t* contigs, const manta_spanning_alignment_t* aligns, const uint32_t* cigar, const uint64_t cigarWords,
+    const uint64_t* bits, const uint64_t bitsWords, std::vector<manta_spanning_select_contig_t>& contigRecs,
+    std::vector<manta_spanning_select_t>& locusRecs)
+{
+  uint64_t nContigs = 0, cigarReach = 0, bitsReach = 0;
+  for (uint32_t l = 0; l < nLoci; ++l) {
+    if (loci[l].status != MANTA_OK) continue;
+    nContigs = std::max<uint64_t>(nContigs, uint64_t(loci[l].first_contig) + loci[l].n_contigs);
+    for (uint32_t c = 0; c < loci[l].n_contigs; ++c) {
+      const uint64_t              i = uint64_t(loci[l].first_contig) + c;
+      const manta_align_result_t& a(aligns[i].align);
+      if (a.status == MANTA_OK) cigarReach = std::max<uint64_t>(cigarReach, std::max(a.cigar1_off + a.cigar1_len, a.cigar2_off + a.cigar2_len));
+      if (isRNA) bitsReach = std::max<uint64_t>(bitsReach, contigs[i].support_off + loci[l].n_words);
+    }
+  }
+  contigRecs.assign(nContigs, manta_spanning_select_contig_t());
+  locusRecs.assign(nLoci, manta_spanning_select_t());
+  if (nLoci == 0) return;
+  if (!ctx) ctx = threadContext();
+  const manta_align_scores_t sc = detail::toAbi(contigFilterScores);
+  const int rc = manta_spanning_select_batch(ctx, &sc, isRNA ? 1 : 0, nLoci, loci, contigs, aligns, cigar, std::min(cigarReach, cigarWords), bits,
+                                             std::min(bitsReach, bitsWords), contigRecs.data(), locusRecs.data());
+  if (detail::selectCallFailed(rc, contigRecs, locusRecs))
+    throw GeneralException("manta_amd spanning contig selection: " + std::string(manta_last_error(ctx)), rc);
+}
+
+/// one locus of the batch: its contigs' jump alignments and, for the RNA rule, the contigs themselves (supportReads; may be nullptr
+/// otherwise)
+struct JumpContigLocusInput {
+  const std::vector<JumpAlignmentResult<int>>* alignments;
+  const Assembly*                              contigs;
+};
+
+struct JumpContigSelection {
+  int best         = -1;        ///< bestAlignmentIndex, -1: the static returned false
+  int deviceStatus = MANTA_OK;  ///< != MANTA_OK: the host function computed this locus
+};
+
+inline int selectJumpContigHost(const AlignmentScores<int>& contigFilterScores, const bool isRNA, const JumpContigLocusInput& in)
+{
+  if (!isRNA) return selectJumpContigDNA(*in.alignments, contigFilterScores);
+  std::vector<unsigned> support;
+  for (const AssembledContig& c : *in.contigs) support.push_back(unsigned(c.supportReads.size()));
+  return selectJumpContigRNA(*in.alignments, support, contigFilterScores);
+}
+
+/// selectJumpContigDNA / selectJumpContigRNA of every locus in ONE device call; a locus the device does not decide (any per-item
+/// status) is recomputed by the host function and carries that status in deviceStatus.
+inline void selectJumpContigBatch(
+    const AlignmentScores<int>& contigFilterScores, const bool isRNA, const std::vector<JumpContigLocusInput>& items,
+    std::vector<JumpContigSelection>& results, manta_ctx_t* ctx = nullptr)
+{
+  const size_t n = items.size();
+  results.assign(n, JumpContigSelection());
+  if (n == 0) return;
+  std::vector<manta_asm_locus_result_t>   loci(n);
+  std::vector<manta_asm_contig_t>         contigs;
+  std::vector<manta_spanning_alignment_t> aligns;
+  std::vector<uint32_t>                   cigar;
+  std::vector<uint64_t>                   bits;
+  for (size_t l = 0; l < n; ++l) {
+    const std::vector<JumpAlignmentResult<int>>& ja(*items[l].alignments);
+    loci[l]              = manta_asm_locus_result_t();
+    loci[l].n_contigs    = uint32_t(ja.size());
+    loci[l].first_contig = uint32_t(contigs.size());
+    unsigned maxRead = 0;
+    if (isRNA)
+      for (const AssembledContig& c : *items[l].contigs)
+        if (!c.supportReads.empty()) maxRead = std::max(maxRead, *c.supportReads.rbegin());
+    loci[l].n_words = maxRead / 64 + 1;
+    for (size_t c = 0; c < ja.size(); ++c) {
+      manta_spanning_alignment_t a = manta_spanning_alignment_t();
+      a.align.score            = ja[c].score;
+      a.align.jump_insert_size = ja[c].jumpInsertSize;
+      a.align.jump_range       = ja[c].jumpRange;
+      a.align.begin_pos1       = ja[c].align1.beginPos;
+      a.align.begin_pos2       = ja[c].align2.beginPos;
+      a.align.cigar1_off       = cigar.size();
+      detail::toPacked(ja[c].align1.apath, cigar);
+      a.align.cigar1_len = uint32_t(cigar.size() - a.align.cigar1_off);
+      a.align.cigar2_off = cigar.size();
+      detail::toPacked(ja[c].align2.apath, cigar);
+      a.align.cigar2_len = uint32_t(cigar.size() - a.align.cigar2_off);
+      aligns.push_back(a);
+      manta_asm_contig_t rec = manta_asm_contig_t();
+      rec.support_off = bits.size();
+      rec.reject_off  = bits.size() + loci[l].n_words;
+      bits.resize(bits.size() + 2 * size_t(loci[l].n_words), 0);
+      if (isRNA)
+        for (const unsigned r : (*items[l].contigs)[c].supportReads) bits[rec.support_off + r / 64] |= uint64_t(1) << (r % 64);
+      contigs.push_back(rec);
+    }
+  }
+  const uint64_t cigarWords = cigar.size(), bitsWords = bits.size();
+  cigar.push_back(0);
+  bits.push_back(0);
+  contigs.push_back(manta_asm_contig_t());
+  aligns.push_back(manta_spanning_alignment_t());
+  std::vector<manta_spanning_select_contig_t> contigRecs;
+  std::vector<manta_spanning_select_t>        locusRecs;
+  selectJumpContigBatch(ctx, contigFilterScores, isRNA, uint32_t(n), loci.data(), contigs.data(), aligns.data(), cigar.data(), cigarWords, bits.data(),
+                        bitsWords, contigRecs, locusRecs);
+  for (size_t l = 0; l < n; ++l) {
+    if (locusRecs[l].status == MANTA_OK) {
+      results[l].best = locusRecs[l].selected ? locusRecs[l].best_contig : -1;
+    } else {
+      results[l].best         = selectJumpContigHost(contigFilterScores, isRNA, items[l]);
+      results[l].deviceStatus = locusRecs[l].status;
+    }
   }
 }
 

@@ -536,6 +536,10 @@ inline void smallSvBatch(
 struct SpanningOutput : AsmOutput {
   std::vector<manta_spanning_alignment_t> aligns;
   std::vector<uint32_t>                   cigar;
+  // contig selection of the batch (selectJumpContigBatch; only with SVCandidateAssemblyRefiner::setDeviceSpanningSelect): `selContigs`
+  // is index-aligned with `aligns`, `selLoci` with `loci`
+  std::vector<manta_spanning_select_contig_t> selContigs;
+  std::vector<manta_spanning_select_t>        selLoci;
 };
 
 /// the fused device pipeline for a batch of spanning loci (references already oriented, in alignment order)
@@ -634,6 +638,10 @@ struct SVCandidateAssemblyRefiner {
   /// still computed by the host functions.  What needs the SVCandidate (setSmallCandSV, the insertion-position exclusion, the two
   /// unknown-size sequences) stays on the host.
   void setDeviceLargeInsertion(const bool on) { _deviceLargeInsertion = on; }
+  /// jump-alignment QC and contig selection of the batched spanning path on the device (default off): one selectJumpContigBatch call
+  /// on the whole batch's output replaces the per-locus selectJumpContigDNA; a locus the device does not decide is still computed by
+  /// that function.  spanningAlignments, extendedContigs and the refined candidate are built as without the switch.
+  void setDeviceSpanningSelect(const bool on) { _deviceSpanningSelect = on; }
 
   /// work counters of this refiner object (no reference counterpart; for logs and tests)
   struct Stats {
@@ -643,6 +651,9 @@ struct SVCandidateAssemblyRefiner {
     /// with setDeviceLargeInsertion and isFindLargeInsertions: loci whose large-insertion search the device decided / that it left to
     /// the host functions (both stay 0 without); largeInsertionAlignments counts the fake-contig alignments of either kind
     uint64_t deviceLargeInsertionLoci = 0, deviceLargeInsertionFallbacks = 0;
+    /// with setDeviceSpanningSelect: spanning loci whose contig selection the device decided / that it left to the host function
+    /// (both stay 0 without)
+    uint64_t deviceSpanningSelectLoci = 0, deviceSpanningSelectFallbacks = 0;
   };
   const Stats&        stats() const { return _stats; }
   const RefinerTimes& times() const { return _times; }
@@ -1235,10 +1246,13 @@ private:
     detail::SpanningOutput& dev(_spanDev);
     detail::spanningBatch(deviceContext(), _spanPipe, _opt.refineOpt.spanningAssembleOpt, _opt.refineOpt.spanningAlignScores, _opt.refineOpt.jumpScore, packed, refs1,
                           refs2, cuts, dev, _hostThreads, _refStage, _ref2Stage);
+    if (_deviceSpanningSelect)  // one call on the whole batch's output, handed back as it came
+      selectJumpContigBatch(deviceContext(), _opt.refineOpt.contigFilterScores, false, uint32_t(loci.size()), dev.loci.data(), dev.contigs.data(),
+                            dev.aligns.data(), dev.cigar.data(), dev.cigar.size(), nullptr, 0, dev.selContigs, dev.selLoci);
     const double tDevice = now();
     _times.device += tDevice - tPacked;
 
-    std::atomic<uint64_t> nContigs(0), nRealigned(0);
+    std::atomic<uint64_t> nContigs(0), nRealigned(0), nDeviceSelect(0), nDeviceSelectFallback(0);
     auto spanningLocus = [&](const size_t l) {
       const SpanningLocus&     sl(loci[l]);
       const Plan&              p(plans[sl.planIndex]);
@@ -1266,7 +1280,14 @@ private:
         getExtendedContig(alignment, data.contigs[c].seq, *sl.align1Ref, *sl.align2Ref, extendedContig);
         data.extendedContigs.push_back(extendedContig);
       }
-      const int best = selectJumpContigDNA(data.spanningAlignments, _opt.refineOpt.contigFilterScores);
+      int best = -1;
+      if (_deviceSpanningSelect && dev.selLoci[l].status == MANTA_OK) {
+        best = dev.selLoci[l].selected ? dev.selLoci[l].best_contig : -1;
+        ++nDeviceSelect;
+      } else {
+        best = selectJumpContigDNA(data.spanningAlignments, _opt.refineOpt.contigFilterScores);
+        if (_deviceSpanningSelect) ++nDeviceSelectFallback;
+      }
       if (best < 0) return;  // bestAlignmentIndex stays 0, no refined candidate (:1392-1397, 1829)
       data.bestAlignmentIndex = unsigned(best);
       data.svs.push_back(p.sv);
@@ -1297,6 +1318,8 @@ private:
     });
     _stats.contigAlignments += nContigs;
     _stats.realignedContigs += nRealigned;
+    _stats.deviceSpanningSelectLoci += nDeviceSelect;
+    _stats.deviceSpanningSelectFallbacks += nDeviceSelectFallback;
     _times.post += now() - tDevice;
   }
 
@@ -1320,6 +1343,7 @@ private:
   PileDumpWriter*               _pileDump = nullptr;
   bool                          _deviceContigQC = false;
   bool                          _deviceLargeInsertion = false;
+  bool                          _deviceSpanningSelect = false;
   mutable std::vector<std::unique_ptr<ReadsTeardown>> _teardowns;  ///< background frees of the current batch call
 };
 

@@ -624,5 +624,32 @@ inline int selectJumpContigDNA(const std::vector<JumpAlignmentResult<int>>& alig
   if (best == -1 || isLowQualityJumpAlignment(alignments[size_t(best)], scores, false)) return -1;
   return best;
 }
+/// selectJumpContigRNA (:1312-1358): index of the selected contig alignment, or -1.  supportReads[i]: contigs[i].supportReads.size().
+/// Every contig that passes the fast QC is tested; among the good ones the highest score (strictly above 0, else the first good one)
+/// is replaced, in index order, by any contig with more than half that score and strictly more support reads than the current choice.
+inline int selectJumpContigRNA(
+    const std::vector<JumpAlignmentResult<int>>& alignments, const std::vector<unsigned>& supportReads, const AlignmentScores<int>& scores)
+{
+  std::vector<unsigned> good;
+  for (size_t i = 0; i < alignments.size(); ++i) {
+    if (isJumpAlignmentQCFail(alignments[i])) continue;
+    if (isLowQualityJumpAlignment(alignments[i], scores, true)) continue;
+    good.push_back(unsigned(i));
+  }
+  if (good.empty()) return -1;
+  int      maxAlnScore = 0;
+  unsigned selected    = good.front();
+  for (const unsigned i : good) {
+    if (alignments[i].score > maxAlnScore) {
+      maxAlnScore = alignments[i].score;
+      selected    = i;
+    }
+  }
+  for (const unsigned i : good) {
+    const bool sufficientScore = 2ll * alignments[i].score > (long long)(maxAlnScore);
+    if (sufficientScore && supportReads[i] > supportReads[selected]) selected = i;
+  }
+  return int(selected);
+}
 
 }  // namespace manta_amd

@@ -96,6 +96,10 @@ int main(int argc, char** argv)
   SVCandidateAssemblyRefiner           refiner(opt, header, src);
   const unsigned hostThreads = argc > 3 ? unsigned(atoi(argv[3])) : std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
   refiner.setHostThreads(hostThreads);
+  // argv[4] (optional, after n, shape and host threads): != 0 turns setDeviceSpanningSelect on; without it nothing changes
+  const bool deviceSelect = argc > 4 && atoi(argv[4]) != 0;
+  refiner.setDeviceSpanningSelect(deviceSelect);
+  if (deviceSelect) std::printf("setDeviceSpanningSelect(true)\n");
   std::vector<SVCandidateAssemblyData> out;
   struct Best {
     double       dt = 1e30;

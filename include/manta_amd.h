@@ -356,6 +356,80 @@ int manta_smallsv_download_large_insertion(manta_smallsv_t* b, manta_large_inser
                                            manta_large_insertion_t* li_out, uint64_t li_cap, uint32_t* cigar_out, uint64_t cigar_cap,
                                            uint64_t* cigar_used);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Small-SV contig ranking and refined candidate ranges: what getSmallSVAssembly does after the contigs' QC to decide which contig of a
+ * locus is used, and which precise candidates come out of it
+ *   the rank-1 / rank-2 rule                            SVCandidateAssemblyRefiner.cpp:2119-2219 (index order; a displaced rank 1
+ *                                                       overwrites rank 2; the swap test's three float ratio tests 0.9f / 1.2f / 1.1f
+ *                                                       exactly as the reference's float expressions decide them)
+ *   setSmallCandSV's ranges and getVariantRange         :677-780, per (first,last) pair of the chosen contig's merged segment list
+ * Read per contig: the alignment's score and is_jumped, the QC record's is_candidate, largest_indel (ContigScoringInfo::variantSize)
+ * and merged list, the popcount of the support bitset (supportReads.size(), pseudo reads included); of the chosen contig also the path,
+ * the contig text and the locus' uncut window.
+ * Limits: at most 64 contigs per locus, else MANTA_E_UNSUPPORTED in the locus' record (never a guess).  A locus one of whose contigs
+ * carries an alignment or QC status other than MANTA_OK carries that status and is left undecided.  A segment index outside the chosen
+ * contig's path, a path whose reference span leaves the window or whose read length differs from the contig's, and a path, segment
+ * list, bitset or text that leaves its arena give the locus MANTA_E_INVALID_ARG; nothing outside is read.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t  status;              /* MANTA_OK or MANTA_E_* for this candidate */
+  uint32_t seg_first, seg_last; /* the path segments: insertAlignment is the path's [seg_first, seg_last] */
+  int32_t  ref_begin, ref_end;  /* refRange, in window coordinates (begin_pos1 already includes the adjusted leading cut) */
+  int32_t  read_begin, read_end; /* readRange: insertSeq is the contig's [read_begin, read_end) */
+  int32_t  cipos_begin;         /* <= 0.  Non-zero is the reference's exception condition (:768), reported with MANTA_OK.  Where the
+                                   reference's index refRange.end_pos() + leftOffset - 1 or readRange.end_pos() + leftOffset - 1 would
+                                   become negative the scan stops and the value reached is reported */
+  int32_t  cipos_end;           /* >= 0: the breakend intervals' width - 1 */
+} manta_small_cand_sv_t;
+
+typedef struct {
+  int32_t  status;      /* MANTA_OK or MANTA_E_* for this locus; the fields below are 0 / -1 unless MANTA_OK */
+  uint32_t selected;    /* some contig nominates a candidate: rank1Contig.isDefined after the swap test */
+  int32_t  best_contig; /* bestAlignmentIndex: a contig of the locus, 0-based; -1 unless selected */
+  int32_t  rank1_contig, rank2_contig; /* as they stand BEFORE the swap test; -1 when undefined */
+  uint32_t rank2_is_best;              /* the swap test's verdict */
+  uint32_t n_candidates;               /* segment pairs of best_contig's merged list: one manta_small_cand_sv_t each */
+  uint64_t cand_off;                   /* of the first one, in the caller's candidate arena */
+} manta_smallsv_select_t;
+
+/* The data arguments are what manta_smallsv_download / manta_smallsv_batch (loci, contigs, alignments, seq_arena, cigar_arena,
+ * bits_arena and their *_used sizes) and manta_smallsv_qc_batch / manta_smallsv_download_qc (qc, seg_arena, *seg_used as
+ * seg_pairs_used) return and what they were given (refs, ref_off), handed straight back.  locus_out[l] belongs to loci[l]; its
+ * candidates are cand_out[cand_off .. cand_off + n_candidates).  cand_cap / *cand_used count records; 32 per locus always suffice.
+ * Per-item failures do not stop the batch: the call returns such an item's code and every other record is valid.  A failure of the
+ * call itself (bad arguments, candidate arena too small, device error) writes no record at all.  The same holds for
+ * manta_smallsv_download_select. */
+int manta_smallsv_select_batch(
+    manta_ctx_t* ctx, uint32_t n_loci, const manta_asm_locus_result_t* loci, const manta_asm_contig_t* contigs,
+    const manta_smallsv_alignment_t* alignments, const manta_smallsv_qc_t* qc, const uint32_t* seg_arena, uint64_t seg_pairs_used,
+    const uint8_t* seq_arena, uint64_t seq_arena_used, const uint32_t* cigar_arena, uint64_t cigar_arena_used, const uint64_t* bits_arena,
+    uint64_t bits_arena_used, const uint8_t* refs, const uint64_t* ref_off, manta_smallsv_select_t* locus_out,
+    manta_small_cand_sv_t* cand_out, uint64_t cand_cap, uint64_t* cand_used);
+
+/* setSmallCandSV's arithmetic by itself (:742-765), one task per (window, contig, begin position, path, segment range) -- what a
+ * caller uses for the large insertion's fake contig.  A segment index past the path, a reference span past the window, a read length
+ * that differs from the contig's and a text or path that leaves its arena are the task's MANTA_E_INVALID_ARG; the error contract is
+ * that of manta_smallsv_select_batch. */
+typedef struct {
+  uint64_t ref_off, contig_off; /* into the caller's sequence arena */
+  uint64_t cigar_off;           /* into the caller's cigar arena */
+  uint32_t ref_len, contig_len, cigar_len;
+  int32_t  begin_pos;           /* align.beginPos, in window coordinates */
+  uint32_t seg_first, seg_last;
+} manta_small_cand_sv_task_t;
+
+int manta_small_cand_sv_batch(
+    manta_ctx_t* ctx, uint32_t n_tasks, const manta_small_cand_sv_task_t* tasks, const uint8_t* seq_arena, uint64_t seq_bytes,
+    const uint32_t* cigar_arena, uint64_t cigar_words, manta_small_cand_sv_t* out);
+
+/* Staged pipeline, opt-in: with the stage set (it needs QC set: MANTA_E_INVALID_ARG without), manta_smallsv_run launches the ranking
+ * behind the QC kernel on data that never left the device; manta_smallsv_download_select returns records index-aligned with the loci[]
+ * of manta_smallsv_download (locus_cap / cand_cap: records the caller's arrays hold).  on == 0 switches the stage off again; a run with
+ * QC switched off does not run it either.  Without the call nothing about run / stats / output_sizes / download / download_qc changes. */
+int manta_smallsv_set_select(manta_smallsv_t* b, int32_t on);
+int manta_smallsv_download_select(manta_smallsv_t* b, manta_smallsv_select_t* locus_out, uint64_t locus_cap, manta_small_cand_sv_t* cand_out,
+                                  uint64_t cand_cap, uint64_t* cand_used);
+
 /* getQuerySeqMatchCount (SVCandidateAssemblyRefiner.cpp:393-418) by itself: counts[i] = number of placements of the query in the
  * target with float(mismatches) / float(query_len) <= max_mismatch_rate, exactly as the reference's float test decides it (a query
  * 'N' always mismatches; query_len == 0 or query_len > target_len: 0).  Any target length, any rate; query_len < 2^32 - 1. */
@@ -578,7 +652,7 @@ typedef struct {
    an older header would be written past its end.  Check both once after loading the library:
      manta_abi_version() == MANTA_ABI_VERSION  and  manta_batch_stats_size() == sizeof(manta_batch_stats_t)
    (manta_amd/_capi.py does).  The version changes whenever a struct of this header changes size or meaning. */
-#define MANTA_ABI_VERSION 7
+#define MANTA_ABI_VERSION 8
 uint32_t manta_abi_version(void);
 uint64_t manta_batch_stats_size(void);
 

@@ -16,7 +16,7 @@ CIGAR_OPS = "MIDNSHP=X"
 ALIGNER_GLOBAL, ALIGNER_LARGE_INDEL, ALIGNER_JUMP = 0, 1, 2
 
 
-ABI_VERSION = 7  # include/manta_amd.h: MANTA_ABI_VERSION
+ABI_VERSION = 8  # include/manta_amd.h: MANTA_ABI_VERSION
 
 
 class MantaError(RuntimeError):
@@ -743,6 +743,7 @@ class SmallSvBatch:
             cig.ctypes.data_as(ctypes.c_void_p), ctypes.c_uint64(cig_cap), ctypes.byref(cu))
         self.lib._check(rc, allow=() if strict else (-5, -6, -7))
         self.raw = (res, contigs, aligns, seq, bits, cig)  # the records and arenas as downloaded (manta_smallsv_qc_batch takes them as they are)
+        self.raw_used = (int(su.value), int(bu.value), int(cu.value))  # ... and what of seq, bits and cig was used
         return _decode_loci("smallsv", self.n_reads, res, contigs, aligns, seq, bits, cig)
 
     def set_qc(self, filter_scores, min_indel):
@@ -764,6 +765,7 @@ class SmallSvBatch:
         f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         rc = f(self.h, qc, ctypes.c_uint64(cap), _p(segs), ctypes.c_uint64(len(segs) // 2), ctypes.byref(used))
         _qc_check(self.lib, rc, qc, cap, strict)
+        self.raw_qc = (qc, segs, int(used.value))  # as downloaded (manta_smallsv_select_batch takes them as they are)
         return _decode_qc(qc, cap, segs)
 
 
@@ -794,6 +796,172 @@ def _download_large_insertion(self, strict=False):
 
 SmallSvBatch.set_large_insertion = _set_large_insertion
 SmallSvBatch.download_large_insertion = _download_large_insertion
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# small-SV contig ranking and refined candidate ranges (manta_smallsv_select_batch / manta_small_cand_sv_batch)
+# ---------------------------------------------------------------------------------------------------------------
+class SmallCandSv(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("seg_first", ctypes.c_uint32), ("seg_last", ctypes.c_uint32)] + [
+        (n, ctypes.c_int32) for n in ("ref_begin", "ref_end", "read_begin", "read_end", "cipos_begin", "cipos_end")]
+
+
+class SmallSvSelect(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("selected", ctypes.c_uint32), ("best_contig", ctypes.c_int32), ("rank1_contig", ctypes.c_int32),
+                ("rank2_contig", ctypes.c_int32), ("rank2_is_best", ctypes.c_uint32), ("n_candidates", ctypes.c_uint32),
+                ("cand_off", ctypes.c_uint64)]
+
+
+class SmallCandSvTask(ctypes.Structure):
+    _fields_ = [("ref_off", ctypes.c_uint64), ("contig_off", ctypes.c_uint64), ("cigar_off", ctypes.c_uint64), ("ref_len", ctypes.c_uint32),
+                ("contig_len", ctypes.c_uint32), ("cigar_len", ctypes.c_uint32), ("begin_pos", ctypes.c_int32), ("seg_first", ctypes.c_uint32),
+                ("seg_last", ctypes.c_uint32)]
+
+
+SS_MAX_CANDS = 32  # candidates a locus can have: the pairs of a merged segment list
+CAND_FIELDS = tuple(n for n, _ in SmallCandSv._fields_)
+SELECT_FIELDS = ("status", "selected", "best_contig", "rank1_contig", "rank2_contig", "rank2_is_best")
+
+
+def _decode_small_select(ls, n_loci, cands):
+    """manta_smallsv_select_t records + candidate arena -> one dict per locus, its candidates as a list of dicts under `candidates`"""
+    out = []
+    for l in range(n_loci):
+        d = {k: int(getattr(ls[l], k)) for k in SELECT_FIELDS}
+        at = int(ls[l].cand_off)
+        d["candidates"] = [{k: int(getattr(cands[at + j], k)) for k in CAND_FIELDS} for j in range(int(ls[l].n_candidates))]
+        out.append(d)
+    return out
+
+
+def _smallsv_select_raw(self, loci, contigs, aligns, qc, segs, seg_pairs, seq, seq_used, cig, cig_used, bits, bits_used, refs, ref_off,
+                        strict=False, locus_out=None, cand_out=None, cand_cap=None):
+    """manta_smallsv_select_batch on records / arenas laid out as manta_smallsv_download and manta_smallsv_download_qc return them (ctypes
+    arrays, numpy arenas and what of each was used) -> one dict per locus (see _decode_small_select).  locus_out / cand_out: the caller's
+    own record arrays (to see what a failed call wrote); cand_cap: what to declare of the candidate arena"""
+    n_loci = len(loci)
+    ls = locus_out if locus_out is not None else (SmallSvSelect * max(n_loci, 1))()
+    cs = cand_out if cand_out is not None else (SmallCandSv * (SS_MAX_CANDS * max(n_loci, 1)))()
+    used = ctypes.c_uint64(0)
+    f = self.lib.manta_smallsv_select_batch
+    f.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 5 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                                                  ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64] + [
+        ctypes.c_void_p] * 4 + [ctypes.c_uint64, ctypes.c_void_p]
+    rc = f(self.ctx, n_loci, loci, contigs, aligns, qc, _p(segs), ctypes.c_uint64(seg_pairs), _p(seq), ctypes.c_uint64(seq_used), _p(cig),
+           ctypes.c_uint64(cig_used), _p(bits), ctypes.c_uint64(bits_used), _p(refs), _p(ref_off), ls, cs,
+           ctypes.c_uint64(len(cs) if cand_cap is None else cand_cap), ctypes.byref(used))
+    carried = {ls[l].status for l in range(n_loci)} if rc != -6 else set()
+    self._check(rc, allow=() if strict else tuple(c for c in carried if c != 0))
+    return _decode_small_select(ls, n_loci, cs)
+
+
+def smallsv_select_arrays(loci_items):
+    """loci_items: per locus (reference window, [contig, ...]) with every contig a dict of `seq`, `begin`, `cigar` (text), `score` and
+    optionally `jumped`, `candidate` (default 1), `largest_indel`, `segments` ([(first, last), ...]: the merged list), `support` (read
+    indices), `status` (of its alignment) and `qc_status` -> the arguments of Lib.smallsv_select_raw, as a dict"""
+    n_loci = len(loci_items)
+    n = sum(len(it[1]) for it in loci_items)
+    loci, contigs, aligns, qc = ((AsmLocusResult * max(n_loci, 1))(), (AsmContig * max(n, 1))(), (SmallSvAlignment * max(n, 1))(),
+                                 (SmallSvQc * max(n, 1))())
+    seq, cig, refs, ref_off, segs, bits = bytearray(), [], bytearray(), [0], [], []
+    i = 0
+    for l, (ref, items) in enumerate(loci_items):
+        n_words = max([1] + [(max(c.get("support", [0]) or [0]) + 64) // 64 for c in items])
+        loci[l].n_contigs, loci[l].first_contig, loci[l].n_words = len(items), i, n_words
+        for c in items:
+            words, cb = pack_cigar(c["cigar"]), _b(c["seq"])
+            contigs[i].seq_off, contigs[i].seq_len = len(seq), len(cb)
+            a = aligns[i].align
+            a.status, a.score, a.is_jumped, a.begin_pos1 = c.get("status", 0), c["score"], int(c.get("jumped", 0)), c["begin"]
+            a.cigar1_off, a.cigar1_len = len(cig), len(words)
+            pairs = c.get("segments", [])
+            qc[i].status, qc[i].is_candidate, qc[i].n_segments = c.get("qc_status", 0), int(c.get("candidate", 1)), len(pairs)
+            qc[i].largest_indel, qc[i].seg_off = c.get("largest_indel", 0), len(segs) // 2
+            for p in pairs:
+                segs += list(p)
+            w = [0] * (2 * n_words)
+            for r in c.get("support", []):
+                w[r // 64] |= 1 << (r % 64)
+            contigs[i].support_off, contigs[i].reject_off = len(bits), len(bits) + n_words
+            bits += w
+            seq += cb
+            cig += words
+            i += 1
+        refs += _b(ref)
+        ref_off.append(len(refs))
+    return dict(loci=loci, contigs=contigs, aligns=aligns, qc=qc, segs=np.array(segs + [0, 0], dtype=np.uint32), seg_pairs=len(segs) // 2,
+                seq=np.frombuffer(bytes(seq) + b"\0", dtype=np.uint8), seq_used=len(seq), cig=np.array(cig + [0], dtype=np.uint32),
+                cig_used=len(cig), bits=np.array(bits + [0], dtype=np.uint64), bits_used=len(bits),
+                refs=np.frombuffer(bytes(refs) + b"\0", dtype=np.uint8), ref_off=np.array(ref_off, dtype=np.uint64))
+
+
+def _smallsv_select_batch(self, loci_items, strict=False):
+    """loci_items as smallsv_select_arrays takes them -> one dict per locus"""
+    return _smallsv_select_raw(self, strict=strict, **smallsv_select_arrays(loci_items))[:len(loci_items)]
+
+
+def _small_cand_sv_raw(self, rec, n, arena, arena_bytes, cig, cig_words, strict=False, out=None):
+    """manta_small_cand_sv_batch on task records and arenas -> one dict per task"""
+    res = out if out is not None else (SmallCandSv * max(n, 1))()
+    f = self.lib.manta_small_cand_sv_batch
+    f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                  ctypes.c_void_p]
+    rc = f(self.ctx, n, rec, _p(arena), ctypes.c_uint64(arena_bytes), _p(cig), ctypes.c_uint64(cig_words), res)
+    carried = {res[i].status for i in range(n)}
+    self._check(rc, allow=() if strict else tuple(c for c in carried if c != 0))
+    return [{k: int(getattr(res[i], k)) for k in CAND_FIELDS} for i in range(n)]
+
+
+def small_cand_sv_arrays(tasks):
+    """tasks: (reference window, contig, begin position, cigar text, seg_first, seg_last) -> (records, n, arena, bytes, cigar arena, words)"""
+    n = len(tasks)
+    rec = (SmallCandSvTask * max(n, 1))()
+    arena, cig = bytearray(), []
+    for i, (ref, contig, begin, cigar, first, last) in enumerate(tasks):
+        rb, cb, words = _b(ref), _b(contig), pack_cigar(cigar)
+        rec[i].ref_off, rec[i].ref_len = len(arena), len(rb)
+        arena += rb
+        rec[i].contig_off, rec[i].contig_len = len(arena), len(cb)
+        arena += cb
+        rec[i].cigar_off, rec[i].cigar_len = len(cig), len(words)
+        cig += words
+        rec[i].begin_pos, rec[i].seg_first, rec[i].seg_last = begin, first, last
+    return rec, n, np.frombuffer(bytes(arena) + b"\0", dtype=np.uint8), len(arena), np.array(cig + [0], dtype=np.uint32), len(cig)
+
+
+def _small_cand_sv_batch(self, tasks, strict=False):
+    """setSmallCandSV's ranges and cipos of every task (see small_cand_sv_arrays) -> one dict per task"""
+    return _small_cand_sv_raw(self, *small_cand_sv_arrays(tasks), strict=strict)
+
+
+Lib.smallsv_select_raw = _smallsv_select_raw
+Lib.smallsv_select_batch = _smallsv_select_batch
+Lib.small_cand_sv_raw = _small_cand_sv_raw
+Lib.small_cand_sv_batch = _small_cand_sv_batch
+
+
+def _set_small_select(self, on=True):
+    """contig ranking and refined candidate ranges behind the QC kernel of every later run (needs set_qc; on False: off again)"""
+    f = self.lib.lib.manta_smallsv_set_select
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+    self.lib._check(f(self.h, int(bool(on))))
+
+
+def _download_small_select(self, strict=False, cand_cap=None):
+    """records of the last run, index-aligned with the locus records of download() -> one dict per locus (see _decode_small_select)"""
+    n_loci = self.n_loci
+    ls, cs = (SmallSvSelect * max(n_loci, 1))(), (SmallCandSv * (SS_MAX_CANDS * max(n_loci, 1)))()
+    used = ctypes.c_uint64(0)
+    f = self.lib.lib.manta_smallsv_download_select
+    f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+    rc = f(self.h, ls, ctypes.c_uint64(max(n_loci, 1)), cs, ctypes.c_uint64(len(cs) if cand_cap is None else cand_cap), ctypes.byref(used))
+    carried = {ls[l].status for l in range(n_loci)} if rc != -6 else set()
+    self.lib._check(rc, allow=() if strict else tuple(c for c in carried if c != 0))
+    return _decode_small_select(ls, n_loci, cs)
+
+
+SmallSvBatch.set_select = _set_small_select
+SmallSvBatch.download_select = _download_small_select
 
 
 def small_sv_text(d):

@@ -995,6 +995,11 @@ int smallsvRunImpl(manta_smallsv_t* b, StageGates* gates)
       smallsvQcLaunch(b);
       stage("qc");
     }
+    b->ssRan = false;
+    if (b->ssOn && b->qcRan) {  // contig ranking and candidate ranges on the QC kernel's records (manta_smallsv_set_select); outside the timed stages
+      smallsvSsLaunch(b);
+      stage("select");
+    }
     b->liRan = false;
     if (b->liOn) {  // large-insertion search on the same data (manta_smallsv_set_large_insertion); outside the timed stages
       smallsvLiLaunch(b);

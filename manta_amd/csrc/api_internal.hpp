@@ -32,6 +32,7 @@
 #include "smallsv_qc_kernels.hpp"
 #include "smallsv_li_kernels.hpp"
 #include "spanning_select_kernels.hpp"
+#include "smallsv_select_kernels.hpp"
 #include <unordered_map>
 #include "rt.hpp"
 #include "host_pool.hpp"
@@ -123,6 +124,9 @@ struct manta_ctx {
   DevBuf dQc[6];   // manta_smallsv_qc_batch / manta_seq_match_count_batch: tasks, records, segments, counters, references, texts
   DevBuf dLi[14];  // manta_smallsv_large_insertion_batch: inputs (tasks, loci, texts, paths, references) and the stage's buffers (LiBufs)
   DevBuf dSel[7];  // manta_spanning_select_batch: tasks, loci, paths, bitsets, contig records, locus records, queue head
+  DevBuf dSs[10];  // manta_smallsv_select_batch / manta_small_cand_sv_batch: tasks, loci, paths, bitsets, segment pairs, texts, windows,
+                   // locus records, candidates, queue head
+  rt::Event evSs[2];  // around smallsv_select_kernel (ssLaunch; read under MANTA_AMD_DEBUG)
   rt::Event evSel[2];  // around spanning_select_kernel (selLaunch; read under MANTA_AMD_DEBUG)
   rt::Stream stream;  // the context's own stream (manta_align_batch / manta_assemble_batch run on it)
   int        deviceId = 0;
@@ -1671,6 +1675,10 @@ struct manta_smallsv : PipeBase {
   manta_align_scores_t  liEdgeScores{}, liCompleteScores{};
   DevBuf                dLi[9];  // the stage's buffers (LI_BUF_*)
   manta_dev::LiParams   liParams{};  // of the last run with the stage set: where its records are
+  // contig ranking and refined candidate ranges behind the QC kernel (manta_smallsv_set_select; off unless asked for, needs QC)
+  bool                  ssOn = false, ssRan = false;
+  manta_dev::QcParams   qcParams{};  // of the last run with QC set: where its inputs and records are
+  DevBuf                dSsLoci, dSsCands, dSsCnt;
   using PipeBase::PipeBase;
 };
 
@@ -1789,7 +1797,8 @@ inline void smallsvQcLaunch(manta_smallsv* b)
   rt::dzero(Q.seg_used, 16);
   rt::launch(smallsv_qc_kernel, qcGrid(b->ctx, nLoci), QC_LDS_BYTES, Q);
   rt::sync();
-  b->qcRan = true;
+  b->qcParams = Q;
+  b->qcRan    = true;
 }
 
 /// device records -> the caller's records and segment arena; recordOf(i): the device record of output item i, nullptr = none (zeroed).
@@ -2147,6 +2156,98 @@ inline void spanningSelLaunch(manta_spanning* b)
   rt::sync();
   selReport(b->ctx, S, "manta_spanning_run");
   b->selRan = true;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// small-SV contig ranking and refined candidate ranges (smallsv_select_kernels.hpp)
+// ------------------------------------------------------------------------------------------------------
+/// the kernel on the inputs `S` names (the stand-alone call's staged records or a pipeline's own state); the caller holds the stream
+inline void ssLaunch(manta_ctx_t* ctx, SsParams& S, DevBuf& locusBuf, DevBuf& candBuf, DevBuf& cntBuf)
+{
+  S.locus_out = locusBuf.as<SsLocusRecDev>(uint64_t(S.n_units) + 1);
+  S.cand_out  = candBuf.as<SsCandDev>(uint64_t(S.n_units) * SS_MAX_CANDS + 1);
+  S.counter   = cntBuf.as<uint32_t>(4);
+  rt::dzero(S.counter, 16);
+  ctx->evSs[0].record();
+  rt::launch(smallsv_select_kernel, qcGrid(ctx, S.n_units), 0, S);
+  ctx->evSs[1].record();
+}
+/// MANTA_AMD_DEBUG: the kernel's own time from its HIP events (the caller has waited for the stream)
+inline void ssReport(manta_ctx_t* ctx, const SsParams& S, const char* who)
+{
+  if (!std::getenv("MANTA_AMD_DEBUG")) return;
+  std::fprintf(stderr, "manta_amd: %s: smallsv_select_kernel %.3f ms for %u loci (HIP events)\n", who, rt::elapsedMs(ctx->evSs[0], ctx->evSs[1]), S.n_units);
+}
+
+inline void ssCandToAbi(const SsCandDev& d, manta_small_cand_sv_t& o)
+{
+  std::memset(&o, 0, sizeof(o));
+  o.status    = d.status;
+  o.seg_first = d.seg_first;
+  o.seg_last  = d.seg_last;
+  if (o.status != MANTA_OK) return;
+  o.ref_begin   = d.ref_begin;
+  o.ref_end     = d.ref_end;
+  o.read_begin  = d.read_begin;
+  o.read_end    = d.read_end;
+  o.cipos_begin = d.cipos_begin;
+  o.cipos_end   = d.cipos_end;
+}
+
+/// device records -> the caller's records and candidate arena.  locusStatus(l): MANTA_OK, or the code of a locus the kernel did not
+/// look at.  A failure of the call as a whole is found before the first record is written.
+template <typename LocusStatus>
+int ssCompact(manta_ctx_t* ctx, const std::vector<SsLocusRecDev>& hLoci, const std::vector<SsCandDev>& hCands, LocusStatus locusStatus,
+              manta_smallsv_select_t* locus_out, manta_small_cand_sv_t* cand_out, uint64_t cand_cap, uint64_t* cand_used, const char* who)
+{
+  auto decided = [&](uint64_t l) { return locusStatus(l) == MANTA_OK && hLoci[l].status == MANTA_OK; };
+  uint64_t total = 0;
+  for (uint64_t l = 0; l < hLoci.size(); ++l) {
+    if (!decided(l)) continue;
+    if (hLoci[l].n_candidates > SS_MAX_CANDS) return fail(ctx, MANTA_E_DEVICE_FAULT, std::string(who) + ": candidate count outside the device arena");
+    total += hLoci[l].n_candidates;
+  }
+  if (total > cand_cap || (total && !cand_out)) return fail(ctx, MANTA_E_CAPACITY, std::string(who) + ": candidate arena too small");
+  uint64_t used  = 0;
+  int      worst = MANTA_OK;
+  for (uint64_t l = 0; l < hLoci.size(); ++l) {
+    manta_smallsv_select_t& o(locus_out[l]);
+    std::memset(&o, 0, sizeof(o));
+    const SsLocusRecDev& d(hLoci[l]);
+    o.status      = (locusStatus(l) != MANTA_OK) ? locusStatus(l) : d.status;
+    o.best_contig = o.rank1_contig = o.rank2_contig = -1;
+    if (o.status != MANTA_OK) {
+      worst = o.status;
+      continue;
+    }
+    o.selected      = d.selected;
+    o.best_contig   = d.best_contig;
+    o.rank1_contig  = d.rank1_contig;
+    o.rank2_contig  = d.rank2_contig;
+    o.rank2_is_best = d.rank2_is_best;
+    o.n_candidates  = d.n_candidates;
+    o.cand_off      = used;
+    for (uint32_t k = 0; k < d.n_candidates; ++k) ssCandToAbi(hCands[l * SS_MAX_CANDS + k], cand_out[used + k]);
+    used += d.n_candidates;
+  }
+  if (cand_used) *cand_used = used;
+  if (worst != MANTA_OK) return fail(ctx, worst, std::string(who) + ": one or more loci failed; see per-item status");
+  return MANTA_OK;
+}
+
+/// the ranking on a finished run's own device state (manta_smallsv_set_select); the caller holds the pipeline's stream and the QC
+/// kernel has ended (smallsvQcLaunch waits for it)
+inline void smallsvSsLaunch(manta_smallsv* b)
+{
+  SsParams S;
+  std::memset(&S, 0, sizeof(S));
+  S.n_units    = b->nLoci;
+  S.qc         = b->qcParams;
+  S.bits_arena = b->asmStage.dBits;
+  ssLaunch(b->ctx, S, b->dSsLoci, b->dSsCands, b->dSsCnt);
+  rt::sync();
+  ssReport(b->ctx, S, "manta_smallsv_run");
+  b->ssRan = true;
 }
 
 inline int checkPiles(manta_ctx_t* ctx, const manta_packed_piles_t* pl, const char* who)

@@ -665,6 +665,218 @@ extern "C" int manta_spanning_download_select(manta_spanning_t* b, manta_spannin
   }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// small-SV contig ranking and refined candidate ranges (smallsv_select_kernels.hpp)
+// ------------------------------------------------------------------------------------------------------
+extern "C" int manta_smallsv_select_batch(
+    manta_ctx_t* ctx, uint32_t n_loci, const manta_asm_locus_result_t* loci, const manta_asm_contig_t* contigs,
+    const manta_smallsv_alignment_t* alignments, const manta_smallsv_qc_t* qc, const uint32_t* seg_arena, uint64_t seg_pairs_used,
+    const uint8_t* seq_arena, uint64_t seq_arena_used, const uint32_t* cigar_arena, uint64_t cigar_arena_used, const uint64_t* bits_arena,
+    uint64_t bits_arena_used, const uint8_t* refs, const uint64_t* ref_off, manta_smallsv_select_t* locus_out,
+    manta_small_cand_sv_t* cand_out, uint64_t cand_cap, uint64_t* cand_used)
+{
+  static const char* fn = "manta_smallsv_select_batch";
+  if (!ctx) return MANTA_E_INVALID_ARG;
+  if (cand_used) *cand_used = 0;
+  if (n_loci && (!loci || !ref_off || !locus_out)) return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": null argument");
+  if (n_loci == 0) return MANTA_OK;
+  uint64_t nContigs = 0;
+  for (uint32_t l = 0; l < n_loci; ++l) {
+    if (ref_off[l + 1] < ref_off[l]) return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": ref_off not monotone");
+    if (loci[l].status != MANTA_OK || loci[l].n_contigs == 0) continue;
+    nContigs = std::max<uint64_t>(nContigs, uint64_t(loci[l].first_contig) + loci[l].n_contigs);
+  }
+  const uint64_t refBytes = ref_off[n_loci];
+  if (nContigs && (!contigs || !alignments || !qc || (seg_pairs_used && !seg_arena) || (seq_arena_used && !seq_arena) ||
+                   (cigar_arena_used && !cigar_arena) || (bits_arena_used && !bits_arena) || (refBytes && !refs)))
+    return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": null argument");
+  try {  // (every allocation sized by the caller's records is inside: nothing may leave through the C boundary)
+    std::vector<uint8_t> seen(nContigs + 1, 0);
+    for (uint32_t l = 0; l < n_loci; ++l) {
+      if (loci[l].status != MANTA_OK) continue;
+      for (uint32_t c = 0; c < loci[l].n_contigs; ++c) {
+        const uint64_t i = uint64_t(loci[l].first_contig) + c;
+        if (seen[i]) return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": contig record " + std::to_string(i) + " belongs to two loci");
+        seen[i] = 1;
+      }
+    }
+    rt::setDevice(ctx->deviceId);
+    rt::ScopedStream onStream(ctx->stream);
+    DevBuf* const   B     = ctx->dSs;
+    const uint32_t* dCig  = B[2].as<uint32_t>(cigar_arena_used + 4);
+    const uint64_t* dBits = B[3].as<uint64_t>(bits_arena_used + 2);
+    const uint32_t* dSegs = B[4].as<uint32_t>(2 * seg_pairs_used + 4);
+    const uint8_t*  dSeq  = B[5].as<uint8_t>(seq_arena_used + 16);
+    const uint8_t*  dRefs = B[6].as<uint8_t>(refBytes + 16);
+    std::vector<SsTaskDev>  hTasks(nContigs + 1);
+    std::vector<SsLocusDev> hLoci(n_loci);
+    auto outside = [](uint64_t off, uint64_t len, uint64_t size) { return off > size || len > size - off; };
+    for (uint32_t l = 0; l < n_loci; ++l) {
+      SsLocusDev& u(hLoci[l]);
+      u.first   = loci[l].first_contig;
+      u.n       = (loci[l].status == MANTA_OK) ? loci[l].n_contigs : 0u;
+      u.status  = loci[l].status;
+      u.ref     = dRefs + ref_off[l];
+      u.ref_len = uint32_t(std::min<uint64_t>(ref_off[l + 1] - ref_off[l], 0xffffffffull));
+      for (uint32_t c = 0; c < u.n; ++c) {
+        const uint64_t              i = uint64_t(u.first) + c;
+        const manta_align_result_t& a(alignments[i].align);
+        SsTaskDev&                  t(hTasks[i]);
+        std::memset(&t, 0, sizeof(t));
+        t.contig  = dSeq;
+        t.cigar   = dCig;
+        t.support = dBits;
+        t.segs    = dSegs;
+        t.status  = (a.status != MANTA_OK) ? a.status : qc[i].status;
+        if (t.status != MANTA_OK) continue;
+        // nothing outside the caller's arenas is ever read
+        if (outside(a.cigar1_off, a.cigar1_len, cigar_arena_used) || outside(qc[i].seg_off, qc[i].n_segments, seg_pairs_used) ||
+            qc[i].n_segments > SS_MAX_CANDS || outside(contigs[i].support_off, loci[l].n_words, bits_arena_used) ||
+            outside(contigs[i].seq_off, contigs[i].seq_len, seq_arena_used)) {
+          t.status = MANTA_E_INVALID_ARG;
+          continue;
+        }
+        t.contig        = dSeq + contigs[i].seq_off;
+        t.contig_len    = contigs[i].seq_len;
+        t.cigar         = dCig + a.cigar1_off;
+        t.n_cigar       = a.cigar1_len;
+        t.support       = dBits + contigs[i].support_off;
+        t.n_words       = loci[l].n_words;
+        t.segs          = dSegs + 2 * qc[i].seg_off;
+        t.n_segs        = qc[i].n_segments;
+        t.begin_pos     = a.begin_pos1;
+        t.score         = a.score;
+        t.is_jumped     = a.is_jumped ? 1u : 0u;
+        t.is_candidate  = qc[i].is_candidate;
+        t.largest_indel = qc[i].largest_indel;
+      }
+    }
+    SsParams S;
+    std::memset(&S, 0, sizeof(S));
+    SsTaskDev*  dTasks = B[0].as<SsTaskDev>(nContigs + 1);
+    SsLocusDev* dLoci  = B[1].as<SsLocusDev>(n_loci);
+    S.tasks   = dTasks;
+    S.units   = dLoci;
+    S.n_units = n_loci;
+    if (cigar_arena_used) rt::h2d(const_cast<uint32_t*>(dCig), cigar_arena, 4 * cigar_arena_used);
+    if (bits_arena_used) rt::h2d(const_cast<uint64_t*>(dBits), bits_arena, 8 * bits_arena_used);
+    if (seg_pairs_used) rt::h2d(const_cast<uint32_t*>(dSegs), seg_arena, 8 * seg_pairs_used);
+    if (seq_arena_used) rt::h2d(const_cast<uint8_t*>(dSeq), seq_arena, seq_arena_used);
+    if (refBytes) rt::h2d(const_cast<uint8_t*>(dRefs), refs, refBytes);
+    rt::h2d(dTasks, hTasks.data(), sizeof(SsTaskDev) * (nContigs + 1));
+    rt::h2d(dLoci, hLoci.data(), sizeof(SsLocusDev) * n_loci);
+    ssLaunch(ctx, S, B[7], B[8], B[9]);
+    std::vector<SsLocusRecDev> hL(n_loci);
+    std::vector<SsCandDev>     hC(uint64_t(n_loci) * SS_MAX_CANDS);
+    rt::d2hAsync(hL.data(), S.locus_out, sizeof(SsLocusRecDev) * n_loci);
+    rt::d2hAsync(hC.data(), S.cand_out, sizeof(SsCandDev) * hC.size());
+    rt::sync();
+    ssReport(ctx, S, fn);
+    return ssCompact(ctx, hL, hC, [&](uint64_t) { return int(MANTA_OK); }, locus_out, cand_out, cand_cap, cand_used, fn);
+  } catch (const std::exception& e) {
+    return fail(ctx, MANTA_E_HIP, e.what());
+  }
+}
+
+extern "C" int manta_small_cand_sv_batch(
+    manta_ctx_t* ctx, uint32_t n_tasks, const manta_small_cand_sv_task_t* tasks, const uint8_t* seq_arena, uint64_t seq_bytes,
+    const uint32_t* cigar_arena, uint64_t cigar_words, manta_small_cand_sv_t* out)
+{
+  static const char* fn = "manta_small_cand_sv_batch";
+  if (!ctx) return MANTA_E_INVALID_ARG;
+  if (n_tasks == 0) return MANTA_OK;
+  if (!tasks || !out || (seq_bytes && !seq_arena) || (cigar_words && !cigar_arena)) return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": null argument");
+  try {
+    rt::setDevice(ctx->deviceId);
+    rt::ScopedStream onStream(ctx->stream);
+    DevBuf* const   B    = ctx->dSs;
+    const uint32_t* dCig = B[2].as<uint32_t>(cigar_words + 4);
+    const uint8_t*  dSeq = B[5].as<uint8_t>(seq_bytes + 16);
+    std::vector<SsCandTaskDev> host(n_tasks);
+    auto outside = [](uint64_t off, uint64_t len, uint64_t size) { return off > size || len > size - off; };
+    for (uint32_t i = 0; i < n_tasks; ++i) {
+      const manta_small_cand_sv_task_t& t(tasks[i]);
+      SsCandTaskDev&                    d(host[i]);
+      std::memset(&d, 0, sizeof(d));
+      d.ref = d.contig = dSeq;
+      d.cigar     = dCig;
+      d.seg_first = t.seg_first;
+      d.seg_last  = t.seg_last;
+      // nothing outside the caller's arenas is ever read
+      if (outside(t.ref_off, t.ref_len, seq_bytes) || outside(t.contig_off, t.contig_len, seq_bytes) || outside(t.cigar_off, t.cigar_len, cigar_words)) {
+        d.status = MANTA_E_INVALID_ARG;
+        continue;
+      }
+      d.ref        = dSeq + t.ref_off;
+      d.contig     = dSeq + t.contig_off;
+      d.cigar      = dCig + t.cigar_off;
+      d.ref_len    = t.ref_len;
+      d.contig_len = t.contig_len;
+      d.n_cigar    = t.cigar_len;
+      d.begin_pos  = t.begin_pos;
+    }
+    SsCandParams P;
+    std::memset(&P, 0, sizeof(P));
+    SsCandTaskDev* dTasks = B[0].as<SsCandTaskDev>(n_tasks);
+    P.tasks   = dTasks;
+    P.n_tasks = n_tasks;
+    P.out     = B[8].as<SsCandDev>(n_tasks);
+    P.counter = B[9].as<uint32_t>(4);
+    if (cigar_words) rt::h2d(const_cast<uint32_t*>(dCig), cigar_arena, 4 * cigar_words);
+    if (seq_bytes) rt::h2d(const_cast<uint8_t*>(dSeq), seq_arena, seq_bytes);
+    rt::h2d(dTasks, host.data(), sizeof(SsCandTaskDev) * n_tasks);
+    rt::dzero(P.counter, 16);
+    rt::launch(small_cand_sv_kernel, qcGrid(ctx, n_tasks), 0, P);
+    std::vector<SsCandDev> hC(n_tasks);
+    rt::d2h(hC.data(), P.out, sizeof(SsCandDev) * n_tasks);
+    int worst = MANTA_OK;
+    for (uint32_t i = 0; i < n_tasks; ++i) {
+      ssCandToAbi(hC[i], out[i]);
+      if (out[i].status != MANTA_OK) worst = out[i].status;
+    }
+    if (worst != MANTA_OK) return fail(ctx, worst, std::string(fn) + ": one or more tasks failed; see per-item status");
+    return MANTA_OK;
+  } catch (const std::exception& e) {
+    return fail(ctx, MANTA_E_HIP, e.what());
+  }
+}
+
+extern "C" int manta_smallsv_set_select(manta_smallsv_t* b, int32_t on)
+{
+  if (!b) return MANTA_E_INVALID_ARG;
+  if (on && !b->qcOn) return fail(b->ctx, MANTA_E_INVALID_ARG, "manta_smallsv_set_select: contig QC is not set (manta_smallsv_set_qc first)");
+  b->ssOn  = on != 0;
+  b->ssRan = false;
+  return MANTA_OK;
+}
+
+extern "C" int manta_smallsv_download_select(manta_smallsv_t* b, manta_smallsv_select_t* locus_out, uint64_t locus_cap,
+                                             manta_small_cand_sv_t* cand_out, uint64_t cand_cap, uint64_t* cand_used)
+{
+  static const char* fn = "manta_smallsv_download_select";
+  if (!b) return MANTA_E_INVALID_ARG;
+  manta_ctx_t* ctx = b->ctx;
+  if (cand_used) *cand_used = 0;
+  if (!b->ran || !b->ssOn || !b->ssRan)
+    return fail(ctx, MANTA_E_INVALID_ARG, std::string(fn) + ": no run with the stage set (manta_smallsv_set_qc, manta_smallsv_set_select, then manta_smallsv_run)");
+  try {
+    rt::setDevice(ctx->deviceId);
+    rt::ScopedStream onStream(b->main);
+    const uint32_t nLoci = b->nLoci;
+    if (nLoci > locus_cap || (nLoci && !locus_out)) return fail(ctx, MANTA_E_CAPACITY, std::string(fn) + ": record array too small");
+    std::vector<AsmLocusOut>   hLoci(nLoci);
+    std::vector<SsLocusRecDev> hL(nLoci);
+    std::vector<SsCandDev>     hC(uint64_t(nLoci) * SS_MAX_CANDS);
+    rt::d2hAsync(hLoci.data(), b->asmStage.dLoci, sizeof(AsmLocusOut) * nLoci);
+    rt::d2hAsync(hL.data(), b->dSsLoci.p, sizeof(SsLocusRecDev) * nLoci);
+    rt::d2hAsync(hC.data(), b->dSsCands.p, sizeof(SsCandDev) * hC.size());
+    rt::sync();
+    return ssCompact(ctx, hL, hC, [&](uint64_t l) { return asmStatusToAbi(hLoci[l].status); }, locus_out, cand_out, cand_cap, cand_used, fn);
+  } catch (const std::exception& e) {
+    return fail(ctx, MANTA_E_HIP, e.what());
+  }
+}
+
 extern "C" int manta_seq_match_count_batch(
     manta_ctx_t* ctx, uint32_t n_tasks, const manta_seq_match_task_t* tasks, const uint8_t* seq_arena, uint64_t seq_bytes, uint32_t* counts)
 {

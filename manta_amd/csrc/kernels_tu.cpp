@@ -26,6 +26,7 @@
 #include "smallsv_qc_kernels.hpp"
 #include "smallsv_li_kernels.hpp"
 #include "spanning_select_kernels.hpp"
+#include "smallsv_select_kernels.hpp"
 #else
 #error "unknown MANTA_TU"
 #endif

@@ -24,7 +24,7 @@
 #define MANTA_TU_ALIGN_PAIR 11  // align_pair_kernel<E>, align_pair_multi_kernel
 #define MANTA_TU_JUMP_PAIR 12   // align_jump_pair_kernel<E>
 #define MANTA_TU_GLUE 13        // pipeline_kernels.hpp, split_kernels.hpp, read_class_kernels.hpp, smallsv_qc_kernels.hpp, smallsv_li_kernels.hpp,
-                                // spanning_select_kernels.hpp
+                                // spanning_select_kernels.hpp, smallsv_select_kernels.hpp
 #define MANTA_TU_ALIGN3 14      // align_kernel<3, E>
 #define MANTA_TU_COUNT 15
 #ifndef MANTA_TU

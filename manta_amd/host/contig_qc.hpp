@@ -55,6 +55,15 @@ inline bool selectCallFailed(const int rc, const std::vector<manta_spanning_sele
     if (l.status == rc) return false;
   return true;
 }
+/// ... and manta_smallsv_select_batch / manta_smallsv_download_select
+inline bool smallSelectCallFailed(const int rc, const std::vector<manta_smallsv_select_t>& loci)
+{
+  if (rc == MANTA_OK) return false;
+  if (rc == MANTA_E_CAPACITY) return true;  // (no per-item code: the candidate arena)
+  for (const manta_smallsv_select_t& l : loci)
+    if (l.status == rc) return false;
+  return true;
+}
 }  // namespace detail
 
 /// one contig alignment of the batch: getSmallSVAssembly's alignment.align, contig.seq and align1RefStr
@@ -404,6 +413,164 @@ inline void selectJumpContigBatch(
     } else {
       results[l].best         = selectJumpContigHost(contigFilterScores, isRNA, items[l]);
       results[l].deviceStatus = locusRecs[l].status;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// small-SV contig ranking and refined candidate ranges (manta_smallsv_select_batch) over the adapter types
+// ------------------------------------------------------------------------------------------------------
+/// The device half alone, on a small-SV batch's own output and its QC records handed back as they came (manta_smallsv_batch /
+/// manta_smallsv_download, manta_smallsv_qc_batch / manta_smallsv_download_qc): locusRecs[l] belongs to loci[l], its candidates are
+/// candRecs[cand_off, cand_off + n_candidates).  A locus whose record carries a status was not decided: the caller recomputes it with
+/// selectSmallSVContig / smallCandSVRanges.  The *Used arguments: what of every arena was used.
+inline void selectSmallSVContigBatch(
+    manta_ctx_t* ctx, const uint32_t nLoci, const manta_asm_locus_result_t* loci, const manta_asm_contig_t* contigs,
+    const manta_smallsv_alignment_t* aligns, const manta_smallsv_qc_t* qc, const uint32_t* segs, const uint64_t segPairsUsed, const uint8_t* seq,
+    const uint64_t seqUsed, const uint32_t* cigar, const uint64_t cigarUsed, const uint64_t* bits, const uint64_t bitsUsed, const uint8_t* refs,
+    const uint64_t* refOff, std::vector<manta_smallsv_select_t>& locusRecs, std::vector<manta_small_cand_sv_t>& candRecs)
+{
+  locusRecs.assign(nLoci, manta_smallsv_select_t());
+  if (candRecs.size() < 32 * size_t(nLoci)) candRecs.resize(32 * size_t(nLoci));
+  if (nLoci == 0) return;
+  if (!ctx) ctx = threadContext();
+  uint64_t  used = 0;
+  const int rc   = manta_smallsv_select_batch(ctx, nLoci, loci, contigs, aligns, qc, segs, segPairsUsed, seq, seqUsed, cigar, cigarUsed, bits, bitsUsed,
+                                              refs, refOff, locusRecs.data(), candRecs.data(), candRecs.size(), &used);
+  if (detail::smallSelectCallFailed(rc, locusRecs))
+    throw GeneralException("manta_amd small-SV contig selection: " + std::string(manta_last_error(ctx)), rc);
+}
+
+/// one locus of the batch: its contigs, their GlobalLargeIndelAligner alignments (beginPos in window coordinates), the contigs' QC
+/// results (findSmallSVCandidateSegments' return value and merged candidateSegments, one per contig) and the uncut reference window
+struct SmallSVSelectLocusInput {
+  const Assembly*                            contigs;
+  const std::vector<AlignmentResult<int>>*   alignments;
+  const std::vector<char>*                   isCandidate;
+  const std::vector<std::vector<segment_t>>* candidateSegments;
+  const std::string*                         refSeq;
+};
+
+struct SmallSVSelection {
+  SmallSVContigChoice            choice;
+  std::vector<segment_t>         segments;    ///< of choice.best: one refined candidate each
+  std::vector<SmallCandSVRanges> candidates;  ///< refRange in window coordinates
+  int                            deviceStatus = MANTA_OK;  ///< != MANTA_OK: the host functions computed this locus
+};
+
+/// the same on the host: the free functions of refiner_util.hpp
+inline void selectSmallSVContigHost(const SmallSVSelectLocusInput& in, SmallSVSelection& r)
+{
+  std::vector<SmallSVContigFacts> facts;
+  for (unsigned c = 0; c < in.alignments->size(); ++c) {
+    if (!(*in.isCandidate)[c]) continue;
+    SmallSVContigFacts f;
+    f.index            = c;
+    f.score            = (*in.alignments)[c].score;
+    f.isJumped         = (*in.alignments)[c].isJumped;
+    f.variantSize      = getLargestIndelSize((*in.alignments)[c].align.apath, (*in.candidateSegments)[c]);
+    f.supportReadCount = unsigned((*in.contigs)[c].supportReads.size());
+    facts.push_back(f);
+  }
+  r.choice = selectSmallSVContig(facts);
+  r.segments.clear();
+  r.candidates.clear();
+  if (r.choice.best < 0) return;
+  const size_t b = size_t(r.choice.best);
+  r.segments = (*in.candidateSegments)[b];
+  for (const segment_t& seg : r.segments) r.candidates.push_back(smallCandSVRanges(*in.refSeq, (*in.contigs)[b].seq, (*in.alignments)[b].align, seg));
+}
+
+/// selectSmallSVContig and smallCandSVRanges of every locus in ONE device call; a locus the device does not decide (any per-item
+/// status) is recomputed by the host functions and carries that status in deviceStatus.
+inline void selectSmallSVContigBatch(const std::vector<SmallSVSelectLocusInput>& items, std::vector<SmallSVSelection>& results, manta_ctx_t* ctx = nullptr)
+{
+  const size_t n = items.size();
+  results.assign(n, SmallSVSelection());
+  if (n == 0) return;
+  std::vector<manta_asm_locus_result_t>  loci(n);
+  std::vector<manta_asm_contig_t>        contigs;
+  std::vector<manta_smallsv_alignment_t> aligns;
+  std::vector<manta_smallsv_qc_t>        qc;
+  std::vector<uint8_t>                   seq, refs;
+  std::vector<uint32_t>                  cigar, segs;
+  std::vector<uint64_t>                  bits, refOff(n + 1, 0);
+  for (size_t l = 0; l < n; ++l) {
+    const SmallSVSelectLocusInput& in(items[l]);
+    loci[l]              = manta_asm_locus_result_t();
+    loci[l].n_contigs    = uint32_t(in.alignments->size());
+    loci[l].first_contig = uint32_t(contigs.size());
+    unsigned maxRead = 0;
+    for (const AssembledContig& c : *in.contigs)
+      if (!c.supportReads.empty()) maxRead = std::max(maxRead, *c.supportReads.rbegin());
+    loci[l].n_words = maxRead / 64 + 1;
+    for (size_t c = 0; c < in.alignments->size(); ++c) {
+      const AlignmentResult<int>& ar((*in.alignments)[c]);
+      const std::string&          text((*in.contigs)[c].seq);
+      manta_smallsv_alignment_t   a = manta_smallsv_alignment_t();
+      a.align.score      = ar.score;
+      a.align.is_jumped  = ar.isJumped ? 1 : 0;
+      a.align.begin_pos1 = ar.align.beginPos;
+      a.align.cigar1_off = cigar.size();
+      detail::toPacked(ar.align.apath, cigar);
+      a.align.cigar1_len = uint32_t(cigar.size() - a.align.cigar1_off);
+      aligns.push_back(a);
+      manta_asm_contig_t rec = manta_asm_contig_t();
+      rec.seq_off     = seq.size();
+      rec.seq_len     = uint32_t(text.size());
+      rec.support_off = bits.size();
+      rec.reject_off  = bits.size() + loci[l].n_words;
+      seq.insert(seq.end(), text.begin(), text.end());
+      bits.resize(bits.size() + 2 * size_t(loci[l].n_words), 0);
+      for (const unsigned r : (*in.contigs)[c].supportReads) bits[rec.support_off + r / 64] |= uint64_t(1) << (r % 64);
+      contigs.push_back(rec);
+      manta_smallsv_qc_t q = manta_smallsv_qc_t();
+      q.is_candidate  = (*in.isCandidate)[c] ? 1u : 0u;
+      q.n_segments    = uint32_t((*in.candidateSegments)[c].size());
+      q.largest_indel = getLargestIndelSize(ar.align.apath, (*in.candidateSegments)[c]);
+      q.seg_off       = segs.size() / 2;
+      for (const segment_t& sg : (*in.candidateSegments)[c]) {
+        segs.push_back(sg.first);
+        segs.push_back(sg.second);
+      }
+      qc.push_back(q);
+    }
+    refs.insert(refs.end(), in.refSeq->begin(), in.refSeq->end());
+    refOff[l + 1] = refs.size();
+  }
+  const uint64_t seqUsed = seq.size(), cigarUsed = cigar.size(), bitsUsed = bits.size(), segPairs = segs.size() / 2;
+  seq.push_back(0);
+  refs.push_back(0);
+  cigar.push_back(0);
+  bits.push_back(0);
+  segs.push_back(0);
+  contigs.push_back(manta_asm_contig_t());
+  aligns.push_back(manta_smallsv_alignment_t());
+  qc.push_back(manta_smallsv_qc_t());
+  std::vector<manta_smallsv_select_t> locusRecs;
+  std::vector<manta_small_cand_sv_t>  candRecs;
+  selectSmallSVContigBatch(ctx, uint32_t(n), loci.data(), contigs.data(), aligns.data(), qc.data(), segs.data(), segPairs, seq.data(), seqUsed,
+                           cigar.data(), cigarUsed, bits.data(), bitsUsed, refs.data(), refOff.data(), locusRecs, candRecs);
+  for (size_t l = 0; l < n; ++l) {
+    SmallSVSelection&             r(results[l]);
+    const manta_smallsv_select_t& d(locusRecs[l]);
+    if (d.status != MANTA_OK) {
+      selectSmallSVContigHost(items[l], r);
+      r.deviceStatus = d.status;
+      continue;
+    }
+    r.choice.rank1       = d.rank1_contig;
+    r.choice.rank2       = d.rank2_contig;
+    r.choice.rank2IsBest = d.rank2_is_best != 0;
+    r.choice.best        = d.selected ? d.best_contig : -1;
+    for (uint32_t k = 0; k < d.n_candidates; ++k) {
+      const manta_small_cand_sv_t& c(candRecs[d.cand_off + k]);
+      SmallCandSVRanges            ranges;
+      ranges.refRange.set_range(c.ref_begin, c.ref_end);
+      ranges.readRange.set_range(c.read_begin, c.read_end);
+      ranges.cipos.set_range(c.cipos_begin, c.cipos_end);
+      r.segments.emplace_back(c.seg_first, c.seg_last);
+      r.candidates.push_back(ranges);
     }
   }
 }

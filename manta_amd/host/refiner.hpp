@@ -136,43 +136,13 @@ inline void addCigarToSpanningAlignment(SVCandidate& sv)
   if (deleteSize) sv.insertAlignment.emplace_back(ALIGNPATH::DELETE, unsigned(deleteSize));
 }
 
-/// how far an indel can slide left/right with unchanged edit distance (:677-717)
-inline known_pos_range2 getVariantRange(
-    const std::string& ref, const known_pos_range2& refRange, const std::string& read, const known_pos_range2& readRange)
-{
-  const pos_t maxRightOffset = std::min(pos_t(ref.size()) - refRange.end_pos(), pos_t(read.size()) - readRange.end_pos());
-  pos_t       rightOffset    = 0;
-  for (; rightOffset < maxRightOffset; ++rightOffset)
-    if (ref[size_t(refRange.begin_pos() + rightOffset)] != read[size_t(readRange.begin_pos() + rightOffset)]) break;
-  const pos_t minLeftOffset = std::max(-refRange.begin_pos(), -readRange.begin_pos());
-  pos_t       leftOffset    = 0;
-  for (; leftOffset >= minLeftOffset; --leftOffset)
-    if (ref[size_t(refRange.end_pos() + leftOffset - 1)] != read[size_t(readRange.end_pos() + leftOffset - 1)]) break;
-  return known_pos_range2(leftOffset, rightOffset);
-}
-
-/// :720-800
+/// :765-800, from the ranges and cipos of smallCandSVRanges (the host's, or a device record's)
 inline void setSmallCandSV(
-    const reference_contig_segment& ref, const std::string& contig, const Alignment& align, const segment_t& segRange, SVCandidate& sv,
-    const GSCOptions& opt)
+    const reference_contig_segment& ref, const std::string& contig, const Alignment& align, const segment_t& segRange,
+    const SmallCandSVRanges& ranges, SVCandidate& sv, const GSCOptions& opt)
 {
   sv.setPrecise();
-  known_pos_range2 readRange, refRange;
-  pos_t            readPos = 0, refPos = align.beginPos;
-  for (unsigned i = 0; i < align.apath.size(); ++i) {
-    const ALIGNPATH::path_segment& ps(align.apath[i]);
-    if (i == segRange.first) {
-      refRange.set_begin_pos(refPos);
-      readRange.set_begin_pos(readPos);
-    }
-    if (ALIGNPATH::is_segment_type_ref_length(ps.type)) refPos += pos_t(ps.length);
-    if (ALIGNPATH::is_segment_type_read_length(ps.type)) readPos += pos_t(ps.length);
-    if (i == segRange.second) {
-      refRange.set_end_pos(refPos);
-      readRange.set_end_pos(readPos);
-    }
-  }
-  const known_pos_range2 cipos(getVariantRange(ref.seq(), refRange, contig, readRange));
+  const known_pos_range2 &readRange(ranges.readRange), &refRange(ranges.refRange), &cipos(ranges.cipos);
   if (cipos.begin_pos() != 0) {
     std::ostringstream oss;
     oss << "Attempting to convert alignment to sv candidate. contigSize: " << contig.size() << " segments: [" << segRange.first << ","
@@ -189,6 +159,13 @@ inline void setSmallCandSV(
   sv.insertSeq        = contig.substr(size_t(readRange.begin_pos()), readRange.size());
   sv.insertAlignment  = ALIGNPATH::path_t(align.apath.begin() + segRange.first, align.apath.begin() + segRange.second + 1);
   if (opt.isOutputContig) sv.contigSeq = contig;
+}
+/// :720-800
+inline void setSmallCandSV(
+    const reference_contig_segment& ref, const std::string& contig, const Alignment& align, const segment_t& segRange, SVCandidate& sv,
+    const GSCOptions& opt)
+{
+  setSmallCandSV(ref, contig, align, segRange, smallCandSVRanges(ref.seq(), contig, align, segRange), sv, opt);  // (refiner_util.hpp)
 }
 
 /// the per-locus host glue after a device batch is independent across loci: spread it over host threads
@@ -421,6 +398,11 @@ struct SmallSvOutput : AsmOutput {
   // contig QC of the batch (manta_smallsv_qc_batch; only with SVCandidateAssemblyRefiner::setDeviceContigQC): index-aligned with `aligns`
   std::vector<manta_smallsv_qc_t>        qc;
   std::vector<uint32_t>                  qcSegs;
+  uint64_t                               seqUsed = 0, bitsUsed = 0, cigarUsed = 0, qcSegPairsUsed = 0;  // what the last batch used of the arenas
+  // contig ranking and candidate ranges of the batch (selectSmallSVContigBatch; only with setDeviceSmallSelect): `selLoci` is
+  // index-aligned with `loci`, a locus' candidates are selCands[cand_off, cand_off + n_candidates)
+  std::vector<manta_smallsv_select_t>    selLoci;
+  std::vector<manta_small_cand_sv_t>     selCands;
   // large-insertion search of the batch (manta_smallsv_large_insertion_batch; only with setDeviceLargeInsertion): `liEdges` is
   // index-aligned with `aligns`, `li` with `loci`
   std::vector<manta_large_insert_edge_t> liEdges;
@@ -443,7 +425,7 @@ struct SmallSvLiRequest {
 inline void smallSvBatch(
     manta_ctx_t* ctx, manta_smallsv_t*& b, const IterativeAssemblerOptions& opt, const AlignmentScores<int>& scores, const int largeIndelScore,
     PackedReads& in, const std::vector<const std::string*>& refs, const std::vector<manta_ref_cuts_t>& cuts, SmallSvOutput& out, const unsigned threads,
-    PinnedArena& refStage, const SmallSvQcRequest* qcRequest = nullptr, const SmallSvLiRequest* liRequest = nullptr)
+    PinnedArena& refStage, const SmallSvQcRequest* qcRequest = nullptr, const SmallSvLiRequest* liRequest = nullptr, const bool isSelect = false)
 {
   if (in.nLoci() == 0) return;
   const manta_asm_options_t  o   = toAbi(opt);
@@ -486,6 +468,9 @@ inline void smallSvBatch(
     // per-item failures (a contig outside the aligner's envelope, ...) are in the per-locus / per-contig status and become
     // that candidate's exception; only a failure of the call itself is fatal here
     if (rc != MANTA_E_UNSUPPORTED && rc != MANTA_E_DEVICE_FAULT && rc != MANTA_E_EMPTY_SEQ) check(rc);
+    out.seqUsed   = su;
+    out.bitsUsed  = bu;
+    out.cigarUsed = cu;
     break;
   }
   if (qcRequest) {
@@ -502,6 +487,11 @@ inline void smallSvBatch(
                                           out.seq.data(), out.cigar.data(), R.bytes, R.off.data(), out.qc.data(), out.qcSegs.data(),
                                           out.qcSegs.size() / 2, &used);
     if (qcCallFailed(rc, out.qc)) check(rc);  // (an item's code is in its record, zeroed above: only the call's own failure is fatal)
+    out.qcSegPairsUsed = used;
+    if (isSelect)  // ... and one on the QC records; a locus the device does not decide keeps its status in the record
+      selectSmallSVContigBatch(ctx, n, out.loci.data(), out.contigs.data(), out.aligns.data(), out.qc.data(), out.qcSegs.data(), out.qcSegPairsUsed,
+                               out.seq.data(), out.seqUsed, out.cigar.data(), out.cigarUsed, out.bits.data(), out.bitsUsed, R.bytes, R.off.data(),
+                               out.selLoci, out.selCands);
   }
   if (liRequest) {
     // likewise one call on the batch's output; a contig or locus the device does not decide keeps its status in the record
@@ -642,6 +632,12 @@ struct SVCandidateAssemblyRefiner {
   /// on the whole batch's output replaces the per-locus selectJumpContigDNA; a locus the device does not decide is still computed by
   /// that function.  spanningAlignments, extendedContigs and the refined candidate are built as without the switch.
   void setDeviceSpanningSelect(const bool on) { _deviceSpanningSelect = on; }
+  /// contig ranking and refined candidate ranges of the batched small-SV path on the device (default off; effective only together with
+  /// setDeviceContigQC(true)): one selectSmallSVContigBatch call on the batch's output and QC records replaces the rank rule and the
+  /// range walk and homology slide of setSmallCandSV.  The device's decision for a locus is used whole or not at all: a locus whose
+  /// record, or one of whose QC records, carries a status is computed by the host functions.  The large-insertion candidate keeps its
+  /// host setSmallCandSV.
+  void setDeviceSmallSelect(const bool on) { _deviceSmallSelect = on; }
 
   /// work counters of this refiner object (no reference counterpart; for logs and tests)
   struct Stats {
@@ -654,6 +650,9 @@ struct SVCandidateAssemblyRefiner {
     /// with setDeviceSpanningSelect: spanning loci whose contig selection the device decided / that it left to the host function
     /// (both stay 0 without)
     uint64_t deviceSpanningSelectLoci = 0, deviceSpanningSelectFallbacks = 0;
+    /// with setDeviceSmallSelect and setDeviceContigQC: small-SV loci whose contig ranking and candidate ranges the device decided /
+    /// that it left to the host functions (both stay 0 without)
+    uint64_t deviceSmallSelectLoci = 0, deviceSmallSelectFallbacks = 0;
   };
   const Stats&        stats() const { return _stats; }
   const RefinerTimes& times() const { return _times; }
@@ -868,12 +867,6 @@ private:
   // ---------------------------------------------------------------------------------------------------------------
   // complex candidates: getSmallSVAssembly (:1921-2303)
   // ---------------------------------------------------------------------------------------------------------------
-  struct ContigScoringInfo {  // :1851-1857
-    bool     isDefined = false;
-    int      score = 0;
-    unsigned index = 0, variantSize = 0;
-    bool     isJumped = false;
-  };
   struct LargeInsertionWork {
     size_t                planIndex = 0;
     unsigned              leftIndex = 0, rightIndex = 0;
@@ -939,13 +932,15 @@ private:
     const detail::SmallSvQcRequest qcRequest{&_opt.refineOpt.contigFilterScores, _opt.scanOpt.minCandidateVariantSize};
     const detail::SmallSvLiRequest liRequest{&_opt.refineOpt.largeInsertEdgeAlignScores, &_opt.refineOpt.largeInsertCompleteAlignScores};
     const bool                     isDeviceLI = _deviceLargeInsertion && isFindLargeInsertions;
+    const bool                     isDeviceSelect = _deviceSmallSelect && _deviceContigQC;
     detail::smallSvBatch(deviceContext(), _smallPipe, _opt.refineOpt.smallSVAssembleOpt, _opt.refineOpt.largeSVAlignScores, _opt.refineOpt.largeGapOpenScore, packed,
-                         refs, cuts, dev, _hostThreads, _refStage, _deviceContigQC ? &qcRequest : nullptr, isDeviceLI ? &liRequest : nullptr);
+                         refs, cuts, dev, _hostThreads, _refStage, _deviceContigQC ? &qcRequest : nullptr, isDeviceLI ? &liRequest : nullptr, isDeviceSelect);
     const double tDevice = now();
     _times.device += tDevice - tPacked;
 
     std::vector<std::unique_ptr<LargeInsertionWork>> liWorkByLocus(which.size());
-    std::atomic<uint64_t>                            nContigs(0), nDeviceQC(0), nDeviceQCFallback(0), nDeviceLI(0), nDeviceLIFallback(0);
+    std::atomic<uint64_t>                            nContigs(0), nDeviceQC(0), nDeviceQCFallback(0), nDeviceLI(0), nDeviceLIFallback(0),
+        nDeviceSelect(0), nDeviceSelectFallback(0);
     auto smallLocus = [&](const size_t w) {
       const Plan&              p(plans[which[w]]);
       SVCandidateAssemblyData& data(out[which[w]]);
@@ -957,13 +952,18 @@ private:
       data.smallSVSegments.resize(contigCount);
       data.largeInsertInfo.resize(contigCount);
       data.extendedContigs.resize(contigCount);
-      ContigScoringInfo     rank1Contig, rank2Contig;
-      std::vector<unsigned> largeInsertionCandidateIndex;
+      std::vector<SmallSVContigFacts> candidateContigs;
+      std::vector<unsigned>           largeInsertionCandidateIndex;
       // the device's search of this locus is used whole or not at all: an item it did not decide sends the locus to the host functions
       bool isLocusDeviceLI = isDeviceLI && dev.li[w].status == MANTA_OK;
       for (unsigned contigIndex = 0; isLocusDeviceLI && contigIndex < contigCount; ++contigIndex)
         isLocusDeviceLI = dev.liEdges[dev.loci[w].first_contig + contigIndex].status == MANTA_OK;
       if (isDeviceLI) ++(isLocusDeviceLI ? nDeviceLI : nDeviceLIFallback);
+      // ... and so is its ranking: the locus' record and every one of its QC records must be clean
+      bool isLocusDeviceSelect = isDeviceSelect && dev.selLoci[w].status == MANTA_OK;
+      for (unsigned contigIndex = 0; isLocusDeviceSelect && contigIndex < contigCount; ++contigIndex)
+        isLocusDeviceSelect = dev.qc[dev.loci[w].first_contig + contigIndex].status == MANTA_OK;
+      if (isDeviceSelect) ++(isLocusDeviceSelect ? nDeviceSelect : nDeviceSelectFallback);
 
       for (unsigned contigIndex = 0; contigIndex < contigCount; ++contigIndex) {
         const AssembledContig&                 contig(data.contigs[contigIndex]);
@@ -1012,51 +1012,48 @@ private:
           }
         }
 
-        if (isSmallSVCandidate) {  // :2115-2166
-          auto refresh = [&](ContigScoringInfo& info) {
-            info.isDefined   = true;
-            info.index       = contigIndex;
-            info.score       = alignment.score;
-            info.variantSize = getLargestIndelSize(alignment.align.apath, candidateSegments);
-            info.isJumped    = alignment.isJumped;
-          };
-          const bool bothJumped    = alignment.isJumped && rank1Contig.isJumped;
-          const bool bothNotJumped = (!alignment.isJumped) && (!rank1Contig.isJumped);
-          if (!rank1Contig.isDefined || (alignment.isJumped && !rank1Contig.isJumped) ||
-              ((bothJumped || bothNotJumped) && alignment.score > rank1Contig.score)) {
-            if (rank1Contig.isDefined) rank2Contig = rank1Contig;
-            refresh(rank1Contig);
-          } else if (!rank2Contig.isDefined || alignment.score > rank2Contig.score) {
-            refresh(rank2Contig);
-          }
+        if (isSmallSVCandidate && !isLocusDeviceSelect) {  // :2115-2166: what the rank rule reads of this contig
+          SmallSVContigFacts facts;
+          facts.index            = contigIndex;
+          facts.score            = alignment.score;
+          facts.isJumped         = alignment.isJumped;
+          facts.variantSize      = getLargestIndelSize(alignment.align.apath, candidateSegments);
+          facts.supportReadCount = unsigned(contig.supportReads.size());
+          candidateContigs.push_back(facts);
         }
       }
-
-      if (rank2Contig.isDefined) {  // :2169-2219
-        const unsigned     n1 = unsigned(data.contigs[rank1Contig.index].supportReads.size());
-        const unsigned     n2 = unsigned(data.contigs[rank2Contig.index].supportReads.size());
-        static const float minScoreRatio(0.9f), minSupportReadCountRatio(1.2f), minVariantSizeRatio(1.1f);
-        const bool         rank1IsSelected = rank1Contig.isJumped && !rank2Contig.isJumped;
-        if (!rank1IsSelected) {
-          const bool rank2IsBest = (rank2Contig.score > (rank1Contig.score * minScoreRatio)) &&
-                                   ((n2 > (n1 * minSupportReadCountRatio)) || (rank2Contig.variantSize > (rank1Contig.variantSize * minVariantSizeRatio)));
-          if (rank2IsBest) rank1Contig = rank2Contig;
+      // :2119-2281: the chosen contig and, per candidate segment, its ranges -- from the device's records or from the host functions
+      int                                                  best = -1;
+      std::vector<std::pair<segment_t, SmallCandSVRanges>> candidates;
+      if (isLocusDeviceSelect) {
+        const manta_smallsv_select_t& sel(dev.selLoci[w]);
+        if (sel.selected) best = sel.best_contig;
+        for (unsigned k = 0; best >= 0 && k < sel.n_candidates; ++k) {
+          const manta_small_cand_sv_t& c(dev.selCands[sel.cand_off + k]);
+          SmallCandSVRanges            ranges;
+          ranges.refRange.set_range(c.ref_begin, c.ref_end);
+          ranges.readRange.set_range(c.read_begin, c.read_end);
+          ranges.cipos.set_range(c.cipos_begin, c.cipos_end);
+          candidates.emplace_back(segment_t(c.seg_first, c.seg_last), ranges);
         }
+      } else {
+        best = selectSmallSVContig(candidateContigs).best;  // (refiner_util.hpp)
+        if (best >= 0)
+          for (const segment_t& segRange : data.smallSVSegments[size_t(best)])
+            candidates.emplace_back(segRange, smallCandSVRanges(align1RefStr, data.contigs[size_t(best)].seq, data.smallSVAlignments[size_t(best)].align, segRange));
       }
-
       std::set<pos_t> insPos;
-      if (rank1Contig.isDefined) {  // :2226-2281
-        data.bestAlignmentIndex = rank1Contig.index;
-        const AssembledContig&        bestContig(data.contigs[data.bestAlignmentIndex]);
-        const AlignmentResult<int>&   bestAlign(data.smallSVAlignments[data.bestAlignmentIndex]);
-        const std::vector<segment_t>  segs(data.smallSVSegments[data.bestAlignmentIndex]);
-        unsigned                      segmentIndex = 0;
-        for (const segment_t& segRange : segs) {
+      if (best >= 0) {
+        data.bestAlignmentIndex = unsigned(best);
+        const AssembledContig&      bestContig(data.contigs[data.bestAlignmentIndex]);
+        const AlignmentResult<int>& bestAlign(data.smallSVAlignments[data.bestAlignmentIndex]);
+        unsigned                    segmentIndex = 0;
+        for (const std::pair<segment_t, SmallCandSVRanges>& cand : candidates) {
           data.svs.push_back(p.sv);
           SVCandidate& newSV(data.svs.back());
           newSV.assemblyAlignIndex   = data.bestAlignmentIndex;
           newSV.assemblySegmentIndex = segmentIndex++;
-          detail::setSmallCandSV(data.bp1ref, bestContig.seq, bestAlign.align, segRange, newSV, _opt);
+          detail::setSmallCandSV(data.bp1ref, bestContig.seq, bestAlign.align, cand.first, cand.second, newSV, _opt);
           if (getExtendedSVType(newSV) == EXTENDED_SV_TYPE::INSERT) insPos.insert(newSV.bp1.interval.range.begin_pos());
         }
       }
@@ -1087,6 +1084,8 @@ private:
     _stats.deviceQCFallbacks += nDeviceQCFallback;
     _stats.deviceLargeInsertionLoci += nDeviceLI;
     _stats.deviceLargeInsertionFallbacks += nDeviceLIFallback;
+    _stats.deviceSmallSelectLoci += nDeviceSelect;
+    _stats.deviceSmallSelectFallbacks += nDeviceSelectFallback;
     std::vector<std::unique_ptr<LargeInsertionWork>> liWork;
     for (auto& w : liWorkByLocus)
       if (w) liWork.push_back(std::move(w));
@@ -1344,6 +1343,7 @@ private:
   bool                          _deviceContigQC = false;
   bool                          _deviceLargeInsertion = false;
   bool                          _deviceSpanningSelect = false;
+  bool                          _deviceSmallSelect = false;
   mutable std::vector<std::unique_ptr<ReadsTeardown>> _teardowns;  ///< background frees of the current batch call
 };
 

@@ -652,4 +652,99 @@ inline int selectJumpContigRNA(
   return int(selected);
 }
 
+// ---- small-SV contig ranking and refined candidate ranges (:677-780, :2119-2219) -------------------------------------
+/// what the rank rule reads of one contig that nominates a candidate (ContigScoringInfo :1851-1857, and the support-read count of the
+/// swap test: contigs[index].supportReads.size())
+struct SmallSVContigFacts {
+  unsigned index = 0;
+  int      score = 0;
+  bool     isJumped = false;
+  unsigned variantSize = 0, supportReadCount = 0;
+};
+struct SmallSVContigChoice {
+  int  rank1 = -1, rank2 = -1;  ///< contig indices as they stand before the swap test, -1: undefined
+  bool rank2IsBest = false;
+  int  best        = -1;  ///< bestAlignmentIndex, -1: no contig nominates
+};
+/// The rank-1 / rank-2 rule over the candidate contigs IN INDEX ORDER (:2119-2166) and the swap test (:2169-2219).  A jumped contig
+/// displaces a non-jumped rank 1 whatever the scores; among equals the strictly higher score wins; a displaced rank 1 overwrites rank
+/// 2 even where that one scores better.  The three ratio tests are the reference's float expressions (int / unsigned -> float, one
+/// float multiply, a float compare): 9 > 10 * 0.9f is false in float and true in double.
+inline SmallSVContigChoice selectSmallSVContig(const std::vector<SmallSVContigFacts>& candidates)
+{
+  SmallSVContigChoice       choice;
+  const SmallSVContigFacts *r1 = nullptr, *r2 = nullptr;
+  for (const SmallSVContigFacts& c : candidates) {
+    const bool rank1Jumped   = r1 && r1->isJumped;
+    const bool bothJumped    = c.isJumped && rank1Jumped;
+    const bool bothNotJumped = (!c.isJumped) && (!rank1Jumped);
+    if (!r1 || (c.isJumped && !rank1Jumped) || ((bothJumped || bothNotJumped) && c.score > r1->score)) {
+      if (r1) r2 = r1;
+      r1 = &c;
+    } else if (!r2 || c.score > r2->score) {
+      r2 = &c;
+    }
+  }
+  if (!r1) return choice;
+  choice.rank1 = int(r1->index);
+  choice.best  = choice.rank1;
+  if (!r2) return choice;
+  choice.rank2 = int(r2->index);
+  static const float minScoreRatio(0.9f), minSupportReadCountRatio(1.2f), minVariantSizeRatio(1.1f);
+  const bool         rank1IsSelected = r1->isJumped && !r2->isJumped;
+  if (!rank1IsSelected) {
+    choice.rank2IsBest = (r2->score > (r1->score * minScoreRatio)) &&
+                         ((r2->supportReadCount > (r1->supportReadCount * minSupportReadCountRatio)) ||
+                          (r2->variantSize > (r1->variantSize * minVariantSizeRatio)));
+    if (choice.rank2IsBest) choice.best = choice.rank2;
+  }
+  return choice;
+}
+
+/// how far an indel can slide left/right with unchanged edit distance (:677-717).  Where the reference's index refRange.end_pos() +
+/// leftOffset - 1 or readRange.end_pos() + leftOffset - 1 would become negative (it reads out of bounds there) the left walk ends
+/// with the value reached.
+inline known_pos_range2 getVariantRange(
+    const std::string& ref, const known_pos_range2& refRange, const std::string& read, const known_pos_range2& readRange)
+{
+  const pos_t maxRightOffset = std::min(pos_t(ref.size()) - refRange.end_pos(), pos_t(read.size()) - readRange.end_pos());
+  pos_t       rightOffset    = 0;
+  for (; rightOffset < maxRightOffset; ++rightOffset)
+    if (ref[size_t(refRange.begin_pos() + rightOffset)] != read[size_t(readRange.begin_pos() + rightOffset)]) break;
+  const pos_t minLeftOffset = std::max(-refRange.begin_pos(), -readRange.begin_pos());
+  pos_t       leftOffset    = 0;
+  for (; leftOffset >= minLeftOffset; --leftOffset) {
+    const pos_t refIndex = refRange.end_pos() + leftOffset - 1, readIndex = readRange.end_pos() + leftOffset - 1;
+    if (refIndex < 0 || readIndex < 0) break;
+    if (ref[size_t(refIndex)] != read[size_t(readIndex)]) break;
+  }
+  return known_pos_range2(leftOffset, rightOffset);
+}
+
+struct SmallCandSVRanges {
+  known_pos_range2 refRange, readRange;  ///< of the path segments [segRange.first, segRange.second]; refRange in `ref`'s coordinates
+  known_pos_range2 cipos;                ///< getVariantRange: begin_pos() != 0 is setSmallCandSV's exception condition (:768)
+};
+/// setSmallCandSV's translation of a segment range into reference and read ranges (:742-762) and its cipos (:765)
+inline SmallCandSVRanges smallCandSVRanges(const std::string& ref, const std::string& contig, const Alignment& align, const segment_t& segRange)
+{
+  SmallCandSVRanges out;
+  pos_t             readPos = 0, refPos = align.beginPos;
+  for (unsigned i = 0; i < align.apath.size(); ++i) {
+    const ALIGNPATH::path_segment& ps(align.apath[i]);
+    if (i == segRange.first) {
+      out.refRange.set_begin_pos(refPos);
+      out.readRange.set_begin_pos(readPos);
+    }
+    if (ALIGNPATH::is_segment_type_ref_length(ps.type)) refPos += pos_t(ps.length);
+    if (ALIGNPATH::is_segment_type_read_length(ps.type)) readPos += pos_t(ps.length);
+    if (i == segRange.second) {
+      out.refRange.set_end_pos(refPos);
+      out.readRange.set_end_pos(readPos);
+    }
+  }
+  out.cipos = getVariantRange(ref, out.refRange, contig, out.readRange);
+  return out;
+}
+
 }  // namespace manta_amd

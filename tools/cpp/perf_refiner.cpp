@@ -100,6 +100,14 @@ int main(int argc, char** argv)
   const bool deviceSelect = argc > 4 && atoi(argv[4]) != 0;
   refiner.setDeviceSpanningSelect(deviceSelect);
   if (deviceSelect) std::printf("setDeviceSpanningSelect(true)\n");
+  // argv[5] (optional): 1 turns setDeviceContigQC and setDeviceSmallSelect on, 2 setDeviceContigQC alone (what the ranking is measured
+  // against: it is effective only together with the QC switch); without it nothing changes
+  const int deviceSmallSelect = argc > 5 ? atoi(argv[5]) : 0;
+  if (deviceSmallSelect != 0) {
+    refiner.setDeviceContigQC(true);
+    refiner.setDeviceSmallSelect(deviceSmallSelect == 1);
+    std::printf("setDeviceContigQC(true) setDeviceSmallSelect(%s)\n", deviceSmallSelect == 1 ? "true" : "false");
+  }
   std::vector<SVCandidateAssemblyData> out;
   struct Best {
     double       dt = 1e30;
